@@ -7,6 +7,9 @@ the per-GPU rate to the reference's 4550 tok/s/GPU on 128x A100
 (BASELINE.md). Weak scaling: per-GPU work fixed as N grows.
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--model llama2_7b]
+                        [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints one JSON line;
+--dump-outputs DIR also saves the last timed step's loss as DIR/loss.npy.
 N>1 is launched by the driver via torch.distributed.run (one rank per GPU).
 """
 
@@ -34,6 +37,15 @@ def main():
                     help="capture the whole training step in a hipGraph "
                          "(N=1; the step is 99.7%% GPU-busy eager, so this "
                          "trims only launch latency)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned to its caller (the training loss) "
+                         "as DIR/loss.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks beyond the "
+                         "headline figure (none exist yet: a plain run "
+                         "already does only setup, warmup and the timed "
+                         "steps, so this changes nothing today)")
     args = ap.parse_args()
 
     from fms_fsdp_amd.config import get_model_config
@@ -171,6 +183,14 @@ def main():
     baseline_per_gpu = 4550.0  # 7B HSDP compile noAC bs2, A100
     vs_baseline = (tokens_per_sec / world) / baseline_per_gpu \
         if args.model == "llama2_7b" else None
+
+    if args.dump_outputs and rank == 0:
+        # inputs and init are seeded above, so two builds run with the same
+        # arguments can be compared output for output
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "loss.npy"),
+                loss.detach().float().cpu().numpy())
 
     if rank == 0:
         print(json.dumps({

@@ -34,6 +34,36 @@ def test_bench_json_contract():
     assert abs(cfg["tok_per_sec_per_gpu"] * d["n_gpus"] - d["value"]) < 1.0
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs DIR writes the last timed step's loss as float32
+    DIR/loss.npy, matching the JSON line's final_loss; the same arguments
+    give the same inputs, so a second run reproduces it. --full is accepted
+    and keeps the one-line contract."""
+    import numpy as np
+
+    def run(out_dir, *extra):
+        out = subprocess.run(
+            [sys.executable, os.path.join(REPO, "bench.py"),
+             "--model", "llama2_test", "--gpus", "1", "--steps", "2",
+             "--warmup", "1", "--batch-size", "1", "--seq-len", "64",
+             "--dump-outputs", str(out_dir), *extra],
+            capture_output=True, text=True, timeout=600, cwd=REPO)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        return json.loads(lines[0]), np.load(os.path.join(out_dir, "loss.npy"))
+
+    d1, l1 = run(tmp_path / "a")
+    d2, l2 = run(tmp_path / "b", "--full")
+    assert os.listdir(tmp_path / "a") == ["loss.npy"]
+    assert l1.dtype == np.float32 and l1.shape == ()
+    assert np.isfinite(l1)
+    assert abs(float(l1) - d1["config"]["final_loss"]) < 1e-4
+    assert d1["steps"] == 2 and d2["steps"] == 2
+    # CPU fp32 path is deterministic: same arguments, same output
+    assert d1["dtype"] == "fp32" and np.array_equal(l1, l2)
+
+
 def test_bench_torchrun_world2_cpu(tmp_path):
     """bench.py under the DRIVER'S exact launch form (torch.distributed.run
     --nnodes=1 --nproc-per-node N ... bench.py --gpus N) at N=2 over
