@@ -14,7 +14,11 @@
 //   A[i][k]: lane l -> i = l&31,          k = (l>>5)*8 + e   (e=0..7)
 //   B[k][j]: lane l -> k = (l>>5)*8 + e,  j = l&31
 //   D[i][j]: lane l, reg r -> j = l&31,   i = (r&3) + 8*(r>>2) + 4*(l>>5)
+#include <cstdlib>
+#include <cstring>
+
 #include "common.h"
+#include "attn_sched.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8v;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -163,14 +167,15 @@ __device__ __forceinline__ unsigned tr_base(int lane, int col, int hb) {
 
 // ---------------------------------------------------------------------
 // Forward. Block = 4 waves x 32 q-rows = 128 q rows; KV tile = 64 keys.
-// grid.x = s/128, grid.y = b*h.
+// 1-D grid of (s/128)*(b*h) workgroups; attn_sched_map() (attn_sched.h)
+// turns the linear id into (q tile, bh).
 // ---------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
     const short* __restrict__ qg, const short* __restrict__ kg,
     const short* __restrict__ vg, short* __restrict__ og,
     float* __restrict__ lseg, int B, int S, int H, int KVH, float scale,
-    long long vstride) {
+    long long vstride, int sched) {
   constexpr int KVB = 64;
   constexpr int NC = D / 16;   // QK^T k-chunks
   constexpr int NT = D / 32;   // 32-wide output tiles
@@ -191,11 +196,13 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
   const int col = lane & 31;   // q-row owner within wave tile
   const int hb = lane >> 5;
 
-  const int bh = blockIdx.y;
+  const AttnWork wk = attn_sched_map(blockIdx.x, S / 128, B * H, sched, false);
+  const int bh = __builtin_amdgcn_readfirstlane(wk.bh);
   const int b = bh / H;
   const int h = bh % H;
   const int kvh = h / (H / KVH);
-  const int q0 = blockIdx.x * 128;        // block q range [q0, q0+128)
+  // block q range [q0, q0+128)
+  const int q0 = __builtin_amdgcn_readfirstlane(wk.tile) * 128;
   const int qw = q0 + wid * 32;           // wave q range
   const int my_q = qw + col;              // this lane's q row
 
@@ -460,7 +467,7 @@ __global__ void attn_bwd_delta_kernel(const short* __restrict__ dog,
 template <int D>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
     const short* __restrict__ kg, const short* __restrict__ dsw,
-    short* __restrict__ dqg, int B, int S, int H, int KVH) {
+    short* __restrict__ dqg, int B, int S, int H, int KVH, int sched) {
   constexpr int KVB = 32;
   constexpr int NT = D / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -475,11 +482,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
   const int col = lane & 31;
   const int hb = lane >> 5;
 
-  const int bh = blockIdx.y;
+  const AttnWork wk = attn_sched_map(blockIdx.x, S / 128, B * H, sched, false);
+  const int bh = __builtin_amdgcn_readfirstlane(wk.bh);
   const int b = bh / H;
   const int h = bh % H;
   const int kvh = h / (H / KVH);
-  const int q0 = blockIdx.x * 128;
+  const int q0 = __builtin_amdgcn_readfirstlane(wk.tile) * 128;
   const int qw = q0 + wid * 32;
   const int my_q = qw + col;
 
@@ -589,8 +597,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
 #undef SIMG
 
 // ---------------------------------------------------------------------
-// Backward dk/dv: grid over KV tiles; each wave owns 32 keys and walks
-// all q-tiles >= its block's kv base. dK/dV accumulate in registers;
+// Backward dk/dv: 1-D grid over (KV tile, bh) via attn_sched_map();
+// each wave owns 32 keys and walks all q-tiles >= its block's kv base.
+// dK/dV accumulate in registers;
 // V stays in registers; K in a per-wave swizzled LDS tile; Q/dO arrive
 // per q-iteration in shared SUBTILED images (coalesced vector staging,
 // plain reads for the S/dP B-operands, tr_read for the dV/dK
@@ -604,7 +613,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
     const float* __restrict__ lseg, const float* __restrict__ deltag,
     void* __restrict__ dkg, void* __restrict__ dvg,
     short* __restrict__ dsw, int B, int S, int H,
-    int KVH, float scale, long long vstride, long long dvstride) {
+    int KVH, float scale, long long vstride, long long dvstride, int sched) {
   constexpr int KVB = 32;   // keys per wave; block = 4 waves = 128 keys
   constexpr int NC = D / 16;
   constexpr int NT = D / 32;
@@ -626,12 +635,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
   const int col = lane & 31;
   const int hb = lane >> 5;
 
-  const int bh = blockIdx.y;
+  // key block 0 walks every q tile: it is the heaviest (heavy_low)
+  const AttnWork wk = attn_sched_map(blockIdx.x, S / 128, B * H, sched, true);
+  const int bh = __builtin_amdgcn_readfirstlane(wk.bh);
+  const int tile = __builtin_amdgcn_readfirstlane(wk.tile);
   const int b = bh / H;
   const int h = bh % H;
   const int kvh = h / (H / KVH);
   const int ngrp = H / KVH;
-  const int kv0 = blockIdx.x * 128 + wid * KVB;
+  const int kv0 = tile * 128 + wid * KVB;
 
   const long long qrow_stride = (long long)H * D;
   const long long krow_stride = (long long)KVH * D;
@@ -671,7 +683,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
     accDK[t] = (f32x16)(0.f);
   }
 
-  const int q_start = (blockIdx.x * 128) / 32 * 32;
+  const int q_start = (tile * 128) / 32 * 32;
   const int t256 = threadIdx.x;
   // thread t owns q row t&31 and ADJACENT column chunks (see the dq
   // kernel's staging comment: cacheline locality matters here);
@@ -831,21 +843,43 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
   }
 }
 
+// Workgroup order of the three causal kernels (attn_sched.h). Default
+// balanced; FMS_AMD_ATTN_SCHED=legacy keeps the former x-fastest
+// (tile, bh) order. Read once; attn_sched_mode() overrides at run time.
+static int g_attn_sched = -1;
+
+static int attn_sched_get() {
+  if (g_attn_sched < 0) {
+    const char* e = getenv("FMS_AMD_ATTN_SCHED");
+    g_attn_sched = (e && strcmp(e, "legacy") == 0) ? ATTN_SCHED_LEGACY
+                                                   : ATTN_SCHED_BALANCED;
+  }
+  return g_attn_sched;
+}
+
 extern "C" {
+
+// mode < 0: query only. Returns the mode in force before the call.
+int attn_sched_mode(int mode) {
+  const int prev = attn_sched_get();
+  if (mode >= 0) g_attn_sched = mode;
+  return prev;
+}
 
 void launch_attn_fwd(const void* q, const void* k, const void* v, void* o,
                      float* lse, int B, int S, int H, int KVH, int D,
                      float scale, long long vstride, hipStream_t stream) {
-  dim3 grid(S / 128, B * H);
+  const unsigned grid = (unsigned)(S / 128) * (unsigned)(B * H);
+  const int sched = attn_sched_get();
   const int lds = 3 * 64 * D * 2;  // single K image + dbuf V
   if (D == 128)
     attn_fwd_kernel<128><<<grid, 256, lds, stream>>>(
         (const short*)q, (const short*)k, (const short*)v, (short*)o, lse, B,
-        S, H, KVH, scale, vstride);
+        S, H, KVH, scale, vstride, sched);
   else
     attn_fwd_kernel<64><<<grid, 256, lds, stream>>>(
         (const short*)q, (const short*)k, (const short*)v, (short*)o, lse, B,
-        S, H, KVH, scale, vstride);
+        S, H, KVH, scale, vstride, sched);
 }
 
 void launch_attn_bwd(const void* do_, const void* q, const void* k,
@@ -858,7 +892,8 @@ void launch_attn_bwd(const void* do_, const void* q, const void* k,
   const long long rows = (long long)B * S * H;
   attn_bwd_delta_kernel<<<(int)((rows * 64 + 255) / 256), 256, 0, stream>>>(
       (const short*)do_, (const short*)o, delta_ws, D, S, H, rows);
-  dim3 grid(S / 128, B * H);
+  const unsigned grid = (unsigned)(S / 128) * (unsigned)(B * H);
+  const int sched = attn_sched_get();
   // dkv FIRST: it publishes the dS workspace the dq kernel consumes
   if (D == 128) {
     const int lds_dkv = 4 * 32 * 128 * 2 + 4 * 32 * 128 * 2 + 4 * 32 * 80;
@@ -866,30 +901,30 @@ void launch_attn_bwd(const void* do_, const void* q, const void* k,
       attn_bwd_dkv_kernel<128, true><<<grid, 256, lds_dkv, stream>>>(
           (const short*)do_, (const short*)q, (const short*)k,
           (const short*)v, lse, delta_ws, dk, dv, (short*)ds_ws, B, S, H,
-          KVH, scale, vstride, dvstride);
+          KVH, scale, vstride, dvstride, sched);
     else
       attn_bwd_dkv_kernel<128, false><<<grid, 256, lds_dkv, stream>>>(
           (const short*)do_, (const short*)q, (const short*)k,
           (const short*)v, lse, delta_ws, dk, dv, (short*)ds_ws, B, S, H,
-          KVH, scale, vstride, dvstride);
+          KVH, scale, vstride, dvstride, sched);
     const int lds_dq = 2 * (32 * 128 * 2 + 32 * 128 * 2);
     attn_bwd_dq_kernel<128><<<grid, 256, lds_dq, stream>>>(
-        (const short*)k, (const short*)ds_ws, (short*)dq, B, S, H, KVH);
+        (const short*)k, (const short*)ds_ws, (short*)dq, B, S, H, KVH, sched);
   } else {
     const int lds_dkv = 4 * 32 * 64 * 2 + 4 * 32 * 64 * 2 + 4 * 32 * 80;
     if (out_bf16)
       attn_bwd_dkv_kernel<64, true><<<grid, 256, lds_dkv, stream>>>(
           (const short*)do_, (const short*)q, (const short*)k,
           (const short*)v, lse, delta_ws, dk, dv, (short*)ds_ws, B, S, H,
-          KVH, scale, vstride, dvstride);
+          KVH, scale, vstride, dvstride, sched);
     else
       attn_bwd_dkv_kernel<64, false><<<grid, 256, lds_dkv, stream>>>(
           (const short*)do_, (const short*)q, (const short*)k,
           (const short*)v, lse, delta_ws, dk, dv, (short*)ds_ws, B, S, H,
-          KVH, scale, vstride, dvstride);
+          KVH, scale, vstride, dvstride, sched);
     const int lds_dq = 2 * (32 * 64 * 2 + 32 * 128 * 2);
     attn_bwd_dq_kernel<64><<<grid, 256, lds_dq, stream>>>(
-        (const short*)k, (const short*)ds_ws, (short*)dq, B, S, H, KVH);
+        (const short*)k, (const short*)ds_ws, (short*)dq, B, S, H, KVH, sched);
   }
 }
 

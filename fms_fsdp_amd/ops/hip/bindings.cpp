@@ -4,6 +4,7 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
 
+#include <string>
 #include <tuple>
 #include <vector>
 
@@ -33,6 +34,7 @@ void launch_attn_bwd(const void*, const void*, const void*, const void*,
                      const void*, const float*, void*, void*, void*, float*,
                      void*, int, int, int, int, int, float, int,
                      long long, long long, hipStream_t);
+int attn_sched_mode(int);
 void launch_cconv_fwd(const void*, const void*, const float*, void*, int,
                       int, int, int, hipStream_t);
 void launch_cconv_bwd(const void*, const void*, const void*, const float*,
@@ -233,6 +235,20 @@ void sq_norm_accum(Tensor t, Tensor out) {
   const int dt = t.scalar_type() == torch::kBFloat16 ? 1
                  : t.scalar_type() == torch::kFloat16 ? 2 : 0;
   launch_sqnorm(t.data_ptr(), dt, out.data_ptr<float>(), n, cur_stream());
+}
+
+// Get/set the causal-attention workgroup order ("balanced" | "legacy",
+// attn_sched.h). Returns the mode in force before the call, so one
+// process can A/B both orders.
+std::string attn_sched_mode_py(c10::optional<std::string> mode) {
+  int m = -1;
+  if (mode.has_value()) {
+    TORCH_CHECK(*mode == "balanced" || *mode == "legacy",
+                "attn_sched_mode: expected 'balanced' or 'legacy', got '",
+                *mode, "'");
+    m = (*mode == "legacy") ? 1 : 0;
+  }
+  return attn_sched_mode(m) == 1 ? "legacy" : "balanced";
 }
 
 std::tuple<Tensor, Tensor> attn_fwd(Tensor q, Tensor k, Tensor v) {
@@ -524,4 +540,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ssd_ygate_bwd", &ssd_ygate_bwd);
   mod.def("attn_fwd", &attn_fwd);
   mod.def("attn_bwd", &attn_bwd);
+  mod.def("attn_sched_mode", &attn_sched_mode_py,
+          pybind11::arg("mode") = pybind11::none());
 }

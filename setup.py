@@ -22,6 +22,8 @@ BUILD_DIR = os.path.join(REPO, "build", "hip_objs")
 HIP_SOURCES = ["rmsnorm.hip", "rope.hip", "swiglu.hip", "cross_entropy.hip",
                "adamw.hip", "attention.hip", "causal_conv1d.hip", "ssd.hip",
                "gemm_nt.hip"]
+# headers the .hip sources include: a newer header rebuilds every object
+HIP_HEADERS = ["common.h", "attn_sched.h"]
 
 
 def compile_hip_objects():
@@ -30,10 +32,10 @@ def compile_hip_objects():
     for src in HIP_SOURCES:
         src_path = os.path.join(HIP_DIR, src)
         obj_path = os.path.join(BUILD_DIR, src.replace(".hip", ".o"))
+        deps = [src_path] + [os.path.join(HIP_DIR, h) for h in HIP_HEADERS]
         if (not os.path.exists(obj_path)
-                or os.path.getmtime(obj_path) < os.path.getmtime(src_path)
-                or os.path.getmtime(obj_path) < os.path.getmtime(
-                    os.path.join(HIP_DIR, "common.h"))):
+                or any(os.path.getmtime(obj_path) < os.path.getmtime(d)
+                       for d in deps)):
             cmd = [os.path.join(ROCM, "bin", "hipcc"),
                    f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
                    "-c", src_path, "-o", obj_path]
