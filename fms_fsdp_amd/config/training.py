@@ -104,3 +104,8 @@ class train_config:
     #                   dynamic loss scaling enabled automatically)
     #   fp32         -> fp32_policy
     mp_policy: str = "auto"
+    # Largest dS workspace (MiB) the attention backward may allocate: the
+    # workspace is (b*h, s, s) bf16, quadratic in seq_length; above the
+    # limit the O(s)-memory recompute backward runs instead (about 7/5 of
+    # the gemm work). 0 = never use the workspace.
+    attn_bwd_workspace_mb: int = 4096

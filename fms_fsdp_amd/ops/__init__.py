@@ -346,6 +346,17 @@ def attention_causal(q, k, v):
     return reference.attention_causal(q, k, v)
 
 
+def attn_bwd_workspace_limit(mb=None):
+    """Get/set the largest dS workspace (MiB) the attention backward may
+    allocate; larger shapes run the O(s)-memory recompute path. 0 = never
+    use the workspace, None = query. Returns the previous value in MiB, or
+    None (and does nothing) without the extension or without a GPU."""
+    if _C is None or not torch.cuda.is_available():
+        return None
+    prev = _C.attn_bwd_ws_limit(None if mb is None else int(mb) << 20)
+    return prev >> 20
+
+
 # --------------------------------------------------------------------------
 # SwiGLU epilogue: silu(g) * u over fused (..., 2H) gate|up
 # --------------------------------------------------------------------------

@@ -19,9 +19,11 @@
 
 #include "common.h"
 #include "attn_sched.h"
+#include "attn_ws.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8v;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) float f32x4v;
 
 union U8 {
   bf16x8v v;
@@ -597,6 +599,197 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
 #undef SIMG
 
 // ---------------------------------------------------------------------
+// Backward dq WITHOUT the dS workspace (O(S) memory): the forward
+// kernel's layout with the online softmax replaced by the saved lse.
+// Each lane owns one q row; Q and dO B-fragments stay in registers for
+// the whole key sweep; K and V 32-key tiles are staged as double-
+// buffered subtiled images. Per key tile:
+//   S^T  = K  Q^T    (A = plain reads of the K image)
+//   dP^T = V dO^T    (A = plain reads of the V image)
+//   p    = exp2(S*scale*log2e - lse*log2e), 0 where key > q
+//   dS   = p * (dP - delta) * scale     -> bf16 B-operand in registers
+//   dq^T += K^T dS^T (A = tr reads of the SAME K image)
+// Formulas, mfma chunk order and the bf16 rounding of dS are those of
+// attn_bwd_dkv_kernel, so both sides of the backward see the same dS.
+// Costs the S and dP chains a second time (7 gemm chains across the
+// backward instead of 5); selected only when the (b*h, s, s) workspace
+// would exceed the limit (attn_ws.h).
+// ---------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(256, 2) void attn_bwd_dq_recompute_kernel(
+    const short* __restrict__ dog, const short* __restrict__ qg,
+    const short* __restrict__ kg, const short* __restrict__ vg,
+    const float* __restrict__ lseg, const float* __restrict__ deltag,
+    short* __restrict__ dqg, int B, int S, int H, int KVH, float scale,
+    long long vstride, int sched) {
+  constexpr int KVB = 32;
+  constexpr int NC = D / 16;
+  constexpr int NT = D / 32;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // double-buffered subtiled images: K (KVB x D) + V (KVB x D), R4 = 8
+  constexpr int IMGB = KVB * D * 2;
+#define KIMG(buf) (smem + ((buf) ? 2 * IMGB : 0))
+#define VIMG(buf) (smem + IMGB + ((buf) ? 2 * IMGB : 0))
+
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col = lane & 31;
+  const int hb = lane >> 5;
+
+  const AttnWork wk = attn_sched_map(blockIdx.x, S / 128, B * H, sched, false);
+  const int bh = __builtin_amdgcn_readfirstlane(wk.bh);
+  const int b = bh / H;
+  const int h = bh % H;
+  const int kvh = h / (H / KVH);
+  const int q0 = __builtin_amdgcn_readfirstlane(wk.tile) * 128;
+  const int qw = q0 + wid * 32;
+  const int my_q = qw + col;
+
+  const long long qrow_stride = (long long)H * D;
+  const long long krow_stride = (long long)KVH * D;
+  const long long qoff = ((long long)b * S * H + (long long)h) * D +
+                         (long long)my_q * qrow_stride;
+  const short* kbase = kg + ((long long)b * S * KVH + (long long)kvh) * D;
+  const short* vbase = vg + (long long)b * S * vstride + (long long)kvh * D;
+
+  // Q / dO -> B-fragments (B[k = feature][j = q]), unscaled like dkv's
+  bf16x8v qb[NC], dob[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    qb[c] = *(const bf16x8v*)(qg + qoff + hb * 8 + c * 16);
+    dob[c] = *(const bf16x8v*)(dog + qoff + hb * 8 + c * 16);
+  }
+  const float lse_q2 = lseg[(long long)bh * S + my_q] * 1.4426950408889634f;
+  const float delta_q = deltag[(long long)bh * S + my_q];
+  const float scale2 = scale * 1.4426950408889634f;
+
+  f32x16 accDQ[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) accDQ[t] = (f32x16)(0.f);
+
+  const int ntiles = (q0 + 128) / KVB;
+  // staging: thread t: key = t&31, column group = t>>5 (D/8 cols). The
+  // next tile is fetched into registers at the top of a tile and written
+  // to the other buffer at its end, so the global latency hides behind
+  // the tile's mfma work.
+  const int skey = threadIdx.x & 31;
+  const int skd0 = (threadIdx.x >> 5) * (D / 8);
+  const short* kp_s = kbase + (long long)skey * krow_stride + skd0;
+  const short* vp_s = vbase + (long long)skey * vstride + skd0;
+  const long long kstep = (long long)KVB * krow_stride;
+  const long long vstep = (long long)KVB * vstride;
+  const int soff0 = SUBT_OFF(skey, skd0, 8);
+  const int soff1 = SUBT_OFF(skey, skd0 + 8, 8);   // D = 128 only
+  f32x4v kpre0, kpre1, vpre0, vpre1;
+#define DQR_FETCH()                                   \
+  do {                                                \
+    kpre0 = *(const f32x4v*)(kp_s);                   \
+    vpre0 = *(const f32x4v*)(vp_s);                   \
+    if constexpr (D == 128) {                         \
+      kpre1 = *(const f32x4v*)(kp_s + 8);             \
+      vpre1 = *(const f32x4v*)(vp_s + 8);             \
+    }                                                 \
+    kp_s += kstep;                                    \
+    vp_s += vstep;                                    \
+  } while (0)
+#define DQR_COMMIT(buf)                               \
+  do {                                                \
+    *(f32x4v*)(KIMG(buf) + soff0) = kpre0;            \
+    *(f32x4v*)(VIMG(buf) + soff0) = vpre0;            \
+    if constexpr (D == 128) {                         \
+      *(f32x4v*)(KIMG(buf) + soff1) = kpre1;          \
+      *(f32x4v*)(VIMG(buf) + soff1) = vpre1;          \
+    }                                                 \
+  } while (0)
+  DQR_FETCH();
+  DQR_COMMIT(0);
+  __syncthreads();
+  // tr-read bases into the K images (R4 = 8)
+  const unsigned ktr = tr_base<1024>(lane, col, hb);
+  const unsigned kib[2] = {(unsigned)(unsigned long long)KIMG(0) + ktr,
+                           (unsigned)(unsigned long long)KIMG(1) + ktr};
+
+  int cur = 0;
+  for (int tile = 0; tile < ntiles; ++tile) {
+    const int kv0 = tile * KVB;
+    const bool more = tile + 1 < ntiles;
+    if (more) DQR_FETCH();
+    // wave-uniform causal skip: key tiles past this wave's last q row
+    // contribute exactly zero (the wave still stages and syncs)
+    if (kv0 <= qw + 31) {
+      f32x16 accS = (f32x16)(0.f), accDP = (f32x16)(0.f);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const int aoff = SUBT_OFF(col, c * 16 + hb * 8, 8);
+        const bf16x8v ka = *(const bf16x8v*)(KIMG(cur) + aoff);
+        const bf16x8v va = *(const bf16x8v*)(VIMG(cur) + aoff);
+        accS = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qb[c], accS, 0, 0, 0);
+        accDP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, dob[c], accDP,
+                                                        0, 0, 0);
+      }
+      // first K^T fragments stream from LDS behind the softmax VALU work
+      const unsigned kbase_t = kib[cur];
+      U2x64 fr[2][2];
+      tr_issue4<0, 128, 512, 640>(kbase_t, fr[0][0], fr[0][1]);
+      const bool partial = (kv0 + 31) > qw;
+      float ds[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float pval = exp2f(accS[r] * scale2 - lse_q2);
+        if (partial && (kv0 + DROW(r, hb)) > my_q) pval = 0.f;
+        ds[r] = pval * (accDP[r] - delta_q) * scale;
+      }
+      // dS^T -> B-operand in registers (two 16-key chunks)
+      const bf16x8v db0 = pack_pT_chunk(ds);
+      const bf16x8v db1 = pack_pT_chunk(ds + 8);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const int pp = t & 1;
+        if (t + 1 < NT) {
+          if (t + 1 == 1)
+            tr_issue4<2048, 2048 + 128, 2048 + 512, 2048 + 640>(
+                kbase_t, fr[1][0], fr[1][1]);
+          else if (t + 1 == 2)
+            tr_issue4<4096, 4096 + 128, 4096 + 512, 4096 + 640>(
+                kbase_t, fr[0][0], fr[0][1]);
+          else
+            tr_issue4<6144, 6144 + 128, 6144 + 512, 6144 + 640>(
+                kbase_t, fr[1][0], fr[1][1]);
+          tr_wait<4>(fr[pp][0], fr[pp][1]);
+        } else {
+          tr_wait<0>(fr[pp][0], fr[pp][1]);
+        }
+        accDQ[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[pp][0].v, db0,
+                                                           accDQ[t], 0, 0, 0);
+        accDQ[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[pp][1].v, db1,
+                                                           accDQ[t], 0, 0, 0);
+      }
+    }
+    if (more) DQR_COMMIT(cur ^ 1);
+    __syncthreads();
+    cur ^= 1;
+  }
+
+  // dS already carries *scale: the epilogue is the workspace dq kernel's
+  short* dqp = dqg + qoff;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int dk0 = t * 32 + 8 * g + 4 * hb;
+      bf16x4 w;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w.v[j] = f2bf(accDQ[t][g * 4 + j]);
+      *(bf16x4*)(dqp + dk0) = w;
+    }
+  }
+}
+#undef DQR_FETCH
+#undef DQR_COMMIT
+#undef KIMG
+#undef VIMG
+
+// ---------------------------------------------------------------------
 // Backward dk/dv: 1-D grid over (KV tile, bh) via attn_sched_map();
 // each wave owns 32 keys and walks all q-tiles >= its block's kv base.
 // dK/dV accumulate in registers;
@@ -606,7 +799,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
 // B-operands). The P/dS lane<->reg transpose goes through a small
 // wave-private LDS buffer. TWO barriers per q-iteration.
 // ---------------------------------------------------------------------
-template <int D, bool OUT_BF16>
+template <int D, bool OUT_BF16, bool PUBLISH_DS>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
     const short* __restrict__ dog, const short* __restrict__ qg,
     const short* __restrict__ kg, const short* __restrict__ vg,
@@ -785,8 +978,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
     // dq kernel consumes it instead of recomputing the S and dP chains
     // (7 gemm chains across the backward -> 5). Vectorized readback from
     // the my_p transpose buffer: lane l covers key l&31, 16B q-chunk
-    // (l>>5)*2 + c.
-    {
+    // (l>>5)*2 + c. Compiled out (PUBLISH_DS = false) on the workspace-
+    // free path, where the dq kernel recomputes dS itself.
+    if constexpr (PUBLISH_DS) {
       const int key = lane & 31;
       const long long grow = ((long long)bh * S + kv0 + key) * S + q0;
 #pragma unroll
@@ -857,7 +1051,73 @@ static int attn_sched_get() {
   return g_attn_sched;
 }
 
+// Largest dS workspace attn_bwd may allocate (attn_ws.h), in bytes.
+// Default 4 GiB; FMS_AMD_ATTN_BWD_WS_MB overrides (MiB, 0 = never use
+// the workspace). Read once; attn_bwd_ws_limit() overrides at run time.
+static long long g_attn_ws_limit = -1;
+
+static long long attn_ws_limit_get() {
+  if (g_attn_ws_limit < 0) {
+    long long mb = ATTN_BWD_WS_DEFAULT_MB;
+    const char* e = getenv("FMS_AMD_ATTN_BWD_WS_MB");
+    if (e && *e) {
+      char* end = nullptr;
+      const long long val = strtoll(e, &end, 10);
+      if (end != e && *end == '\0' && val >= 0 && val <= (1LL << 40)) mb = val;
+    }
+    g_attn_ws_limit = mb << 20;
+  }
+  return g_attn_ws_limit;
+}
+
+// Backward kernels for one head dim. ds_ws != null: dkv publishes dS, dq
+// consumes it. ds_ws == null: workspace-free, dkv keeps dS to itself and
+// dq recomputes it (no ordering dependency between the two kernels).
+template <int D>
+static void attn_bwd_launch(const void* do_, const void* q, const void* k,
+                            const void* v, const float* lse, void* dq,
+                            void* dk, void* dv, float* delta_ws, void* ds_ws,
+                            int B, int S, int H, int KVH, float scale,
+                            int out_bf16, long long vstride,
+                            long long dvstride, hipStream_t stream) {
+  const unsigned grid = (unsigned)(S / 128) * (unsigned)(B * H);
+  const int sched = attn_sched_get();
+  const int lds_dkv = 4 * 32 * D * 2 + 4 * 32 * D * 2 + 4 * 32 * 80;
+#define DKV_LAUNCH(OUT, PUB)                                                  \
+  attn_bwd_dkv_kernel<D, OUT, PUB><<<grid, 256, lds_dkv, stream>>>(           \
+      (const short*)do_, (const short*)q, (const short*)k, (const short*)v,   \
+      lse, delta_ws, dk, dv, (short*)ds_ws, B, S, H, KVH, scale, vstride,     \
+      dvstride, sched)
+  if (ds_ws) {
+    // dkv FIRST: it publishes the dS workspace the dq kernel consumes
+    if (out_bf16)
+      DKV_LAUNCH(true, true);
+    else
+      DKV_LAUNCH(false, true);
+    const int lds_dq = 2 * (32 * D * 2 + 32 * 128 * 2);
+    attn_bwd_dq_kernel<D><<<grid, 256, lds_dq, stream>>>(
+        (const short*)k, (const short*)ds_ws, (short*)dq, B, S, H, KVH, sched);
+  } else {
+    if (out_bf16)
+      DKV_LAUNCH(true, false);
+    else
+      DKV_LAUNCH(false, false);
+    const int lds_dq = 2 * (32 * D * 2 + 32 * D * 2);   // dbuf K + V images
+    attn_bwd_dq_recompute_kernel<D><<<grid, 256, lds_dq, stream>>>(
+        (const short*)do_, (const short*)q, (const short*)k, (const short*)v,
+        lse, delta_ws, (short*)dq, B, S, H, KVH, scale, vstride, sched);
+  }
+#undef DKV_LAUNCH
+}
+
 extern "C" {
+
+// bytes < 0: query only. Returns the limit in force before the call.
+long long attn_bwd_ws_limit(long long bytes) {
+  const long long prev = attn_ws_limit_get();
+  if (bytes >= 0) g_attn_ws_limit = bytes;
+  return prev;
+}
 
 // mode < 0: query only. Returns the mode in force before the call.
 int attn_sched_mode(int mode) {
@@ -892,40 +1152,12 @@ void launch_attn_bwd(const void* do_, const void* q, const void* k,
   const long long rows = (long long)B * S * H;
   attn_bwd_delta_kernel<<<(int)((rows * 64 + 255) / 256), 256, 0, stream>>>(
       (const short*)do_, (const short*)o, delta_ws, D, S, H, rows);
-  const unsigned grid = (unsigned)(S / 128) * (unsigned)(B * H);
-  const int sched = attn_sched_get();
-  // dkv FIRST: it publishes the dS workspace the dq kernel consumes
-  if (D == 128) {
-    const int lds_dkv = 4 * 32 * 128 * 2 + 4 * 32 * 128 * 2 + 4 * 32 * 80;
-    if (out_bf16)
-      attn_bwd_dkv_kernel<128, true><<<grid, 256, lds_dkv, stream>>>(
-          (const short*)do_, (const short*)q, (const short*)k,
-          (const short*)v, lse, delta_ws, dk, dv, (short*)ds_ws, B, S, H,
-          KVH, scale, vstride, dvstride, sched);
-    else
-      attn_bwd_dkv_kernel<128, false><<<grid, 256, lds_dkv, stream>>>(
-          (const short*)do_, (const short*)q, (const short*)k,
-          (const short*)v, lse, delta_ws, dk, dv, (short*)ds_ws, B, S, H,
-          KVH, scale, vstride, dvstride, sched);
-    const int lds_dq = 2 * (32 * 128 * 2 + 32 * 128 * 2);
-    attn_bwd_dq_kernel<128><<<grid, 256, lds_dq, stream>>>(
-        (const short*)k, (const short*)ds_ws, (short*)dq, B, S, H, KVH, sched);
-  } else {
-    const int lds_dkv = 4 * 32 * 64 * 2 + 4 * 32 * 64 * 2 + 4 * 32 * 80;
-    if (out_bf16)
-      attn_bwd_dkv_kernel<64, true><<<grid, 256, lds_dkv, stream>>>(
-          (const short*)do_, (const short*)q, (const short*)k,
-          (const short*)v, lse, delta_ws, dk, dv, (short*)ds_ws, B, S, H,
-          KVH, scale, vstride, dvstride, sched);
-    else
-      attn_bwd_dkv_kernel<64, false><<<grid, 256, lds_dkv, stream>>>(
-          (const short*)do_, (const short*)q, (const short*)k,
-          (const short*)v, lse, delta_ws, dk, dv, (short*)ds_ws, B, S, H,
-          KVH, scale, vstride, dvstride, sched);
-    const int lds_dq = 2 * (32 * 64 * 2 + 32 * 128 * 2);
-    attn_bwd_dq_kernel<64><<<grid, 256, lds_dq, stream>>>(
-        (const short*)k, (const short*)ds_ws, (short*)dq, B, S, H, KVH, sched);
-  }
+  if (D == 128)
+    attn_bwd_launch<128>(do_, q, k, v, lse, dq, dk, dv, delta_ws, ds_ws, B, S,
+                         H, KVH, scale, out_bf16, vstride, dvstride, stream);
+  else
+    attn_bwd_launch<64>(do_, q, k, v, lse, dq, dk, dv, delta_ws, ds_ws, B, S,
+                        H, KVH, scale, out_bf16, vstride, dvstride, stream);
 }
 
 }  // extern "C"

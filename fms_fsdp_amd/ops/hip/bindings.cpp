@@ -8,6 +8,8 @@
 #include <tuple>
 #include <vector>
 
+#include "attn_ws.h"
+
 using torch::Tensor;
 
 extern "C" {
@@ -35,6 +37,7 @@ void launch_attn_bwd(const void*, const void*, const void*, const void*,
                      void*, int, int, int, int, int, float, int,
                      long long, long long, hipStream_t);
 int attn_sched_mode(int);
+long long attn_bwd_ws_limit(long long);
 void launch_cconv_fwd(const void*, const void*, const float*, void*, int,
                       int, int, int, hipStream_t);
 void launch_cconv_bwd(const void*, const void*, const void*, const float*,
@@ -251,6 +254,19 @@ std::string attn_sched_mode_py(c10::optional<std::string> mode) {
   return attn_sched_mode(m) == 1 ? "legacy" : "balanced";
 }
 
+// Get/set the largest dS workspace attn_bwd may allocate, in bytes
+// (attn_ws.h; 0 = always workspace-free). Returns the limit in force
+// before the call.
+int64_t attn_bwd_ws_limit_py(c10::optional<int64_t> bytes) {
+  long long v = -1;
+  if (bytes.has_value()) {
+    TORCH_CHECK(*bytes >= 0, "attn_bwd_ws_limit: expected bytes >= 0, got ",
+                *bytes);
+    v = *bytes;
+  }
+  return attn_bwd_ws_limit(v);
+}
+
 std::tuple<Tensor, Tensor> attn_fwd(Tensor q, Tensor k, Tensor v) {
   CHECK_BF16_CONTIG(q);
   CHECK_BF16_CONTIG(k);
@@ -295,13 +311,17 @@ std::tuple<Tensor, Tensor, Tensor> attn_bwd(Tensor do_, Tensor q, Tensor k,
   // dS workspace (b, h, s, s) bf16: written by dkv, consumed by dq —
   // the backward's P/dP recompute runs once instead of twice. ~2.1 GB
   // at the 7B shape; the caching allocator reuses it across layers.
-  auto ds_ws = torch::empty({(long long)b * h, (long long)s, (long long)s},
-                            q.options());
+  // Quadratic in s, so above attn_bwd_ws_limit no workspace is allocated
+  // and the launcher runs the O(s)-memory recompute path (null ds_ws).
+  Tensor ds_ws;
+  if (attn_bwd_use_workspace(b, h, s, attn_bwd_ws_limit(-1)))
+    ds_ws = torch::empty({(long long)b * h, (long long)s, (long long)s},
+                         q.options());
   const float scale = 1.f / sqrtf((float)d);
   launch_attn_bwd(do_.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
                   o.data_ptr(), lse.data_ptr<float>(), dq.data_ptr(),
                   dk.data_ptr(), dv.data_ptr(), delta.data_ptr<float>(),
-                  ds_ws.data_ptr(), b, s,
+                  ds_ws.defined() ? ds_ws.data_ptr() : nullptr, b, s,
                   h, kvh, d, scale, out_bf16 ? 1 : 0, vs, dvs, cur_stream());
   if (out_bf16) return {dq, dk, dv};
   return {dq, dk.to(torch::kBFloat16), dv.to(torch::kBFloat16)};
@@ -542,4 +562,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("attn_bwd", &attn_bwd);
   mod.def("attn_sched_mode", &attn_sched_mode_py,
           pybind11::arg("mode") = pybind11::none());
+  mod.def("attn_bwd_ws_limit", &attn_bwd_ws_limit_py,
+          pybind11::arg("bytes") = pybind11::none());
 }

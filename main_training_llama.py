@@ -10,6 +10,7 @@ import sys
 
 import torch
 import torch.distributed as dist
+from fms_fsdp_amd import ops
 from fms_fsdp_amd.config import train_config, update_config, get_model_config
 from fms_fsdp_amd.models import Llama, LlamaBlock
 from fms_fsdp_amd.parallel import ShardedModel, ShardedAdamW
@@ -69,6 +70,7 @@ def main(**kwargs):
     if torch.cuda.is_available():
         torch.cuda.set_device(local_rank)
     setup_environ_flags()
+    ops.attn_bwd_workspace_limit(cfg.attn_bwd_workspace_mb)
 
     if rank == 0:
         print(f"--> running with these configs {cfg}")

@@ -23,7 +23,7 @@ HIP_SOURCES = ["rmsnorm.hip", "rope.hip", "swiglu.hip", "cross_entropy.hip",
                "adamw.hip", "attention.hip", "causal_conv1d.hip", "ssd.hip",
                "gemm_nt.hip"]
 # headers the .hip sources include: a newer header rebuilds every object
-HIP_HEADERS = ["common.h", "attn_sched.h"]
+HIP_HEADERS = ["common.h", "attn_sched.h", "attn_ws.h"]
 
 
 def compile_hip_objects():

@@ -18,6 +18,7 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
+from fms_fsdp_amd import ops
 from fms_fsdp_amd.config import train_config, update_config, get_model_config
 from fms_fsdp_amd.models import Llama, LlamaBlock
 from fms_fsdp_amd.models.speculator import MLPSpeculator
@@ -46,6 +47,7 @@ def main(**kwargs):
     if torch.cuda.is_available():
         torch.cuda.set_device(local_rank)
     setup_environ_flags()
+    ops.attn_bwd_workspace_limit(cfg.attn_bwd_workspace_mb)
     device = torch.device("cuda", local_rank) if torch.cuda.is_available() \
         else torch.device("cpu")
 
