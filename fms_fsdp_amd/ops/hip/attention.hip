@@ -469,7 +469,8 @@ __global__ void attn_bwd_delta_kernel(const short* __restrict__ dog,
 template <int D>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
     const short* __restrict__ kg, const short* __restrict__ dsw,
-    short* __restrict__ dqg, int B, int S, int H, int KVH, int sched) {
+    short* __restrict__ dqg, int B, int S, int H, int KVH, int sched,
+    int ws_tiled) {
   constexpr int KVB = 32;
   constexpr int NT = D / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -511,7 +512,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
   const int skd0 = sgrp * (D / 8);
   const short* kp_s = kbase + (long long)skey * krow_stride + skd0;
   const long long kstep = (long long)KVB * krow_stride;
-  const short* sp_s = dsbase + (long long)skey * S + sgrp * 16;
+  // row-major workspace [bh][key][q], or the key-lane dkv kernel's tiles
+  // [bh][key/32][q/32][q%32/16][key%32][q%16]: a thread's 16 q are 32 B
+  // contiguous either way, and a key tile step is 32*S elements in both
+  const short* sp_s =
+      ws_tiled ? dsw + (long long)bh * S * S +
+                     (long long)(q0 / 32 + (sgrp >> 1)) * 1024 +
+                     (sgrp & 1) * 512 + skey * 16
+               : dsbase + (long long)skey * S + sgrp * 16;
   const long long sstep = (long long)KVB * S;
   const int koff = SUBT_OFF(skey, skd0, 8);
   const int koff1 = SUBT_OFF(skey, skd0 + 8, 8);
@@ -1037,6 +1045,353 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
   }
 }
 
+// ---------------------------------------------------------------------
+// Backward dk/dv, KEY ON THE LANE (default body; the kernel above stays
+// selectable as FMS_AMD_ATTN_DKV=legacy). Same grid, staging images and
+// formulas; the S and dP chains run with their operands swapped,
+//   S  = Q  K^T   (A = plain reads of the Q image,  B = K tile)
+//   dP = dO V^T   (A = plain reads of the dO image, B = V registers)
+// so the accumulators are S[q][key]: lane&31 is the key and register r
+// is q row DROW(r, hb). P and dS then ARE the B-operand of
+//   dV^T[feat][key] += dO^T P     dK^T[feat][key] += Q^T dS
+// straight from the lane's own registers: the k-slice order of an mfma
+// is free as long as A agrees, so slice kc takes registers kc*8..kc*8+7
+// (q rows 16kc + 4hb + {0..3} and 16kc + 8 + 4hb + {0..3}) and A reads
+// exactly those two 4-row groups of the image with ds_read_b64_tr_b16.
+// No P/dS transpose buffer, no LDS round trip, ONE barrier per q step.
+//  - lse*log2e and delta are per register now: the waves stage the 32+32
+//    floats of the next q step into a double-buffered 256 B region.
+//  - The next Q/dO chunks are fetched into registers once the softmax
+//    math of a step is done and committed to the other image at its end.
+//  - dS is published from registers: a permlane32_swap per register pair
+//    (pack_pT_chunk) gives each lane 8 consecutive q of its key row. The
+//    workspace is tiled (ws_tiled, see pub_off below): one store
+//    instruction of a wave writes 1 KB contiguously, and the dq kernel's
+//    staging reads 1 KB per 32 lanes.
+//  - The [feat][key] accumulators are transposed per 32-feature block
+//    through the wave's own K tile (free after the loop), so the stores
+//    and GQA atomics keep the row = key, 128 B-per-half-wave pattern.
+// ---------------------------------------------------------------------
+template <int O>
+__device__ __forceinline__ void tr_issue4x2(unsigned b0, unsigned b1,
+                                            U2x64& r0, U2x64& r1) {
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %4 offset:%c6\n\t"
+      "ds_read_b64_tr_b16 %1, %5 offset:%c7\n\t"
+      "ds_read_b64_tr_b16 %2, %4 offset:%c8\n\t"
+      "ds_read_b64_tr_b16 %3, %5 offset:%c9"
+      : "=&v"(r0.u[0]), "=&v"(r0.u[1]), "=&v"(r1.u[0]), "=&v"(r1.u[1])
+      : "v"(b0), "v"(b1), "i"(O), "i"(O + 256), "i"(O + 512), "i"(O + 768)
+      : "memory");
+}
+
+// fragments of 32-feature block t (t is a constant after unrolling)
+__device__ __forceinline__ void kl_issue(int t, unsigned b0, unsigned b1,
+                                         U2x64& r0, U2x64& r1) {
+  switch (t) {
+    case 0: tr_issue4x2<0>(b0, b1, r0, r1); break;
+    case 1: tr_issue4x2<2048>(b0, b1, r0, r1); break;
+    case 2: tr_issue4x2<4096>(b0, b1, r0, r1); break;
+    default: tr_issue4x2<6144>(b0, b1, r0, r1); break;
+  }
+}
+
+// B-operand slice from 8 accumulator registers, in register order
+__device__ __forceinline__ bf16x8v pack_slice(const float* p) {
+  U8 b;
+  b.u[0] = pack2(p[0], p[1]);
+  b.u[1] = pack2(p[2], p[3]);
+  b.u[2] = pack2(p[4], p[5]);
+  b.u[3] = pack2(p[6], p[7]);
+  return b.v;
+}
+
+template <int D, bool OUT_BF16, bool PUBLISH_DS>
+__global__ __launch_bounds__(256, D == 64 ? 3 : 2) void
+attn_bwd_dkv_keylane_kernel(
+    const short* __restrict__ dog, const short* __restrict__ qg,
+    const short* __restrict__ kg, const short* __restrict__ vg,
+    const float* __restrict__ lseg, const float* __restrict__ deltag,
+    void* __restrict__ dkg, void* __restrict__ dvg,
+    short* __restrict__ dsw, int B, int S, int H,
+    int KVH, float scale, long long vstride, long long dvstride, int sched,
+    int ws_tiled) {
+  constexpr int KVB = 32;   // keys per wave; block = 4 waves = 128 keys
+  constexpr int NC = D / 16;
+  constexpr int NT = D / 32;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* k_lds = smem;                           // [4][KVB][D*2] per-wave
+  constexpr int IMGB = 32 * D * 2;
+#define QIMG(buf) (smem + 4 * KVB * D * 2 + ((buf) ? 2 * IMGB : 0))
+#define DOIMG(buf) (smem + 4 * KVB * D * 2 + IMGB + ((buf) ? 2 * IMGB : 0))
+  // row constants of a q step: [2][32 lse*log2e | 32 delta] fp32
+  float* rowc = (float*)(smem + 4 * KVB * D * 2 + 4 * IMGB);
+
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col = lane & 31;
+  const int hb = lane >> 5;
+
+  const AttnWork wk = attn_sched_map(blockIdx.x, S / 128, B * H, sched, true);
+  const int bh = __builtin_amdgcn_readfirstlane(wk.bh);
+  const int tile = __builtin_amdgcn_readfirstlane(wk.tile);
+  const int b = bh / H;
+  const int h = bh % H;
+  const int kvh = h / (H / KVH);
+  const int ngrp = H / KVH;
+  const int kv0 = tile * 128 + wid * KVB;
+
+  const long long qrow_stride = (long long)H * D;
+  const long long krow_stride = (long long)KVH * D;
+  const short* qbase = qg + ((long long)b * S * H + (long long)h) * D;
+  const short* dobase = dog + ((long long)b * S * H + (long long)h) * D;
+  const short* kbase = kg + ((long long)b * S * KVH + (long long)kvh) * D;
+  const short* vbase = vg + (long long)b * S * vstride + (long long)kvh * D;
+
+  char* my_k = k_lds + wid * KVB * D * 2;
+
+  // this wave's K rows, staged once as a subtiled image
+  {
+    constexpr int CHUNKS = KVB * D / 8;     // 16 B chunks
+    for (int i = lane; i < CHUNKS; i += 64) {
+      const int row = i / (D / 8);
+      const int cb = (i % (D / 8)) * 8;
+      const long long g = (long long)(kv0 + row) * krow_stride + cb;
+      *(f32x4*)(my_k + SUBT_OFF(row, cb, 8)) = *(const f32x4*)(kbase + g);
+    }
+  }
+  // V fragments stay in registers (B-operand column = this lane's key)
+  bf16x8v vreg[NC];
+  {
+    const short* vp = vbase + (long long)(kv0 + col) * vstride + hb * 8;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) vreg[c] = *(const bf16x8v*)(vp + c * 16);
+  }
+
+  f32x16 accDV[NT], accDK[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    accDV[t] = (f32x16)(0.f);
+    accDK[t] = (f32x16)(0.f);
+  }
+
+  const int q_start = tile * 128;
+  const int t256 = threadIdx.x;
+  // staging as in the kernel above: thread t owns q row t&31 and adjacent
+  // column chunks. Every wave also carries the step's row constants, even
+  // waves lse (pre-multiplied by log2e), odd waves delta, row = lane & 31
+  // (duplicates write the same value to the same slot). The loop body is
+  // branch-free so that the compiler schedules it as one block: the last
+  // step re-fetches its own rows into the image nobody reads again.
+  const int sq = t256 & 31;
+  const int sd0 = (t256 >> 5) * ((D == 128) ? 16 : 8);
+  // uniform row pointers + one 32-bit per-thread offset (Q and dO share
+  // their layout): the loop carries scalars, not 64-bit vector pointers
+  const short* qp_s = qbase + (long long)q_start * qrow_stride;
+  const short* dop_s = dobase + (long long)q_start * qrow_stride;
+  const int goff = sq * (int)qrow_stride + sd0;
+  const long long qstep = 32 * qrow_stride;
+  const int soff0 = SUBT_OFF(sq, sd0, 8);
+  const int soff1 = SUBT_OFF(sq, sd0 + 8, 8);
+  const int rcw = wid & 1;
+  const float* rc_s = (rcw ? deltag : lseg) + (long long)bh * S + q_start;
+  const float rc_mul = rcw ? 1.0f : 1.4426950408889634f;
+  f32x4v qpre0, qpre1, dpre0, dpre1;
+  float rcpre = 0.f;
+#define DKV_FETCH()                                   \
+  do {                                                \
+    qpre0 = *(const f32x4v*)(qp_s + goff);            \
+    dpre0 = *(const f32x4v*)(dop_s + goff);           \
+    if constexpr (D == 128) {                         \
+      qpre1 = *(const f32x4v*)(qp_s + goff + 8);      \
+      dpre1 = *(const f32x4v*)(dop_s + goff + 8);     \
+    }                                                 \
+    rcpre = rc_s[col];                                \
+  } while (0)
+#define DKV_ADVANCE(on)                               \
+  do {                                                \
+    qp_s += (on) ? qstep : 0;                         \
+    dop_s += (on) ? qstep : 0;                        \
+    rc_s += (on) ? 32 : 0;                            \
+  } while (0)
+#define DKV_COMMIT(buf)                               \
+  do {                                                \
+    *(f32x4v*)(QIMG(buf) + soff0) = qpre0;            \
+    *(f32x4v*)(DOIMG(buf) + soff0) = dpre0;           \
+    if constexpr (D == 128) {                         \
+      *(f32x4v*)(QIMG(buf) + soff1) = qpre1;          \
+      *(f32x4v*)(DOIMG(buf) + soff1) = dpre1;         \
+    }                                                 \
+    rowc[(buf) * 64 + rcw * 32 + col] = rcpre * rc_mul; \
+  } while (0)
+  DKV_FETCH();
+  DKV_COMMIT(0);
+  __syncthreads();
+
+  // tr-read bases into the Q/dO images (R4 = 8): in-subtile lane column,
+  // row group hb of a slice (128 B), 16-lane column block. The second
+  // read of a fragment sits two row groups on, where the image's 16 B
+  // row-group XOR is set: it gets the ^16 base.
+  const unsigned tr0 =
+      (unsigned)((lane & 15) * 8 + hb * 128 + (col >> 4) * 1024);
+  const unsigned tr1 = tr0 ^ 16u;
+  const float scale2 = scale * 1.4426950408889634f;
+  const int key = kv0 + col;
+  // dS workspace address = uniform base + q0 * pub_qmul + lane part; the
+  // second slice sits pub_kc elements on. Row-major [bh][key][q]: lane
+  // (key, hb) stores q 16kc + 8hb .. +7 of its key row. Tiled
+  // [bh][key/32][q/32][kc][key%32][16 q]: the same 16 B land at
+  // kc*1 KB + (2 key + hb)*16 B, so one store instruction of the wave
+  // writes 1 KB contiguously and a tile is 2 KB.
+  const int pub_off = ws_tiled ? col * 16 + hb * 8 : col * S + hb * 8;
+  const int pub_kc = ws_tiled ? 512 : 16;
+  const int pub_qmul = ws_tiled ? 32 : 1;
+  short* pub_base =
+      dsw + (long long)bh * S * S +
+      (ws_tiled ? (long long)(kv0 / 32) * S * 32 : (long long)kv0 * S);
+
+  int cur = 0;
+  for (int q0 = q_start; q0 < S; q0 += 32) {
+    const bool more = q0 + 32 < S;
+
+    f32x16 accS = (f32x16)(0.f), accDP = (f32x16)(0.f);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int boff = SUBT_OFF(col, c * 16 + hb * 8, 8);
+      const bf16x8v ka = *(const bf16x8v*)(my_k + boff);
+      const bf16x8v qbf = *(const bf16x8v*)(QIMG(cur) + boff);
+      const bf16x8v dbf = *(const bf16x8v*)(DOIMG(cur) + boff);
+      accS = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qbf, ka, accS, 0, 0, 0);
+      accDP = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dbf, vreg[c], accDP,
+                                                      0, 0, 0);
+    }
+
+    // row constants of registers 4g..4g+3: q rows 8g + 4hb + {0..3}
+    const f32x4v* lse4 = (const f32x4v*)(rowc + cur * 64) + hb;
+    const f32x4v* del4 = (const f32x4v*)(rowc + cur * 64 + 32) + hb;
+    const unsigned dob = (unsigned)(unsigned long long)DOIMG(cur);
+    const unsigned qib = (unsigned)(unsigned long long)QIMG(cur);
+    float pv[16], ds[16];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const f32x4v lse_q2 = lse4[2 * g];
+      const f32x4v delta_q = del4[2 * g];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = g * 4 + j;
+        const int q = q0 + DROW(r, hb);
+        float pval = exp2f(accS[r] * scale2 - lse_q2[j]);
+        if (key > q) pval = 0.f;
+        pv[r] = pval;
+        ds[r] = pval * (accDP[r] - delta_q[j]) * scale;
+      }
+    }
+    const bf16x8v pb0 = pack_slice(pv), pb1 = pack_slice(pv + 8);
+    const bf16x8v db0 = pack_slice(ds), db1 = pack_slice(ds + 8);
+
+    // keep the phases apart in the schedule: hoisting the fetch or the
+    // publish shuffles into the softmax math costs more registers than the
+    // 256 this kernel has
+    __builtin_amdgcn_sched_barrier(0);
+    // fetch the next q step now that S, dP and the fp32 P/dS are dead (the
+    // registers do not reach further up); the dV and dK chains cover the
+    // latency. Ahead of the publish stores, so that the commit's counted
+    // wait on these loads leaves the stores in flight.
+    DKV_ADVANCE(more);
+    DKV_FETCH();
+    __builtin_amdgcn_sched_barrier(0);
+
+    // publish this (32-key x 32-q) dS tile, 16 B per lane and slice
+    if constexpr (PUBLISH_DS) {
+      short* grow = pub_base + (long long)q0 * pub_qmul;   // uniform
+      *(bf16x8v*)(grow + pub_off) = pack_pT_chunk(ds);
+      *(bf16x8v*)(grow + pub_off + pub_kc) = pack_pT_chunk(ds + 8);
+    }
+
+    __builtin_amdgcn_sched_barrier(0);
+
+    U2x64 fr[2][2];
+    kl_issue(0, dob + tr0, dob + tr1, fr[0][0], fr[0][1]);
+#define DKV_KLLOOP(ACC, B0, B1, BASE, NEXT_ISSUE)                            \
+  do {                                                                       \
+    _Pragma("unroll") for (int t = 0; t < NT; ++t) {                         \
+      const int pp = t & 1;                                                  \
+      if (t + 1 < NT) {                                                      \
+        kl_issue(t + 1, (BASE) + tr0, (BASE) + tr1, fr[pp ^ 1][0],           \
+                 fr[pp ^ 1][1]);                                             \
+        tr_wait<4>(fr[pp][0], fr[pp][1]);                                    \
+      } else {                                                               \
+        NEXT_ISSUE;                                                          \
+      }                                                                      \
+      ACC[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[pp][0].v, B0,      \
+                                                       ACC[t], 0, 0, 0);     \
+      ACC[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr[pp][1].v, B1,      \
+                                                       ACC[t], 0, 0, 0);     \
+    }                                                                        \
+  } while (0)
+    // dV^T += dO^T P; its last block overlaps the first Q^T fragments.
+    // NT is even, so the last block sits in fr[1] and fr[0] is free.
+    DKV_KLLOOP(accDV, pb0, pb1, dob,
+               (kl_issue(0, qib + tr0, qib + tr1, fr[0][0], fr[0][1]),
+                tr_wait<4>(fr[1][0], fr[1][1])));
+    // dK^T += Q^T dS
+    DKV_KLLOOP(accDK, db0, db1, qib, (tr_wait<0>(fr[1][0], fr[1][1])));
+#undef DKV_KLLOOP
+
+    DKV_COMMIT(cur ^ 1);
+    __syncthreads();
+    cur ^= 1;
+  }
+#undef DKV_FETCH
+#undef DKV_ADVANCE
+#undef DKV_COMMIT
+#undef QIMG
+#undef DOIMG
+
+  // write dK/dV. acc[t][r] is (feat t*32 + DROW(r, hb), key col):
+  // transpose each 32x32 fp32 block through this wave's K tile (no other
+  // wave touches it; DS ops of a wave execute in order) with a 16 B
+  // chunk XOR on the key, then store as the kernel above does: register
+  // r = key row DROW(r, hb), lane = feature, 128 B per half-wave.
+  auto flush = [&](const f32x16& acc, int t, void* outg, long long rstride) {
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      f32x4v w;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w[j] = acc[g * 4 + j];
+      *(f32x4v*)(my_k + col * 128 + (((2 * g + hb) ^ (col & 7)) * 16)) = w;
+    }
+    __builtin_amdgcn_wave_barrier();
+    // uniform row base per register + one 32-bit lane offset (the 4*hb
+    // rows and the feature). dv may target a strided slice of a fused
+    // dqkv buffer: rstride is its row stride.
+    const long long ubase = ((long long)b * S + kv0) * rstride +
+                            (long long)kvh * D + t * 32;
+    const int loff = 4 * hb * (int)rstride + col;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int krel = DROW(r, hb);
+      const float val = *(const float*)(my_k + krel * 128 +
+                                        (((col >> 2) ^ (krel & 7)) * 16) +
+                                        (col & 3) * 4);
+      const long long uoff = ubase + (long long)DROW(r, 0) * rstride;
+      if (OUT_BF16) {
+        ((short*)outg + uoff)[loff] = f2bf(val);
+      } else if (ngrp > 1) {
+        atomicAdd((float*)outg + uoff + loff, val);
+      } else {
+        ((float*)outg + uoff)[loff] += val;
+      }
+    }
+  };
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    flush(accDK[t], t, dkg, (long long)(KVH * D));
+    flush(accDV[t], t, dvg, dvstride);
+  }
+}
+
 // Workgroup order of the three causal kernels (attn_sched.h). Default
 // balanced; FMS_AMD_ATTN_SCHED=legacy keeps the former x-fastest
 // (tile, bh) order. Read once; attn_sched_mode() overrides at run time.
@@ -1070,6 +1425,22 @@ static long long attn_ws_limit_get() {
   return g_attn_ws_limit;
 }
 
+// dk/dv kernel body: key-on-the-lane (default) or the former key-on-the-
+// register body with its LDS transpose buffer. FMS_AMD_ATTN_DKV=legacy
+// selects the latter. Read once; attn_dkv_mode() overrides at run time.
+#define ATTN_DKV_KEYLANE 0
+#define ATTN_DKV_LEGACY 1
+static int g_attn_dkv = -1;
+
+static int attn_dkv_get() {
+  if (g_attn_dkv < 0) {
+    const char* e = getenv("FMS_AMD_ATTN_DKV");
+    g_attn_dkv = (e && strcmp(e, "legacy") == 0) ? ATTN_DKV_LEGACY
+                                                 : ATTN_DKV_KEYLANE;
+  }
+  return g_attn_dkv;
+}
+
 // Backward kernels for one head dim. ds_ws != null: dkv publishes dS, dq
 // consumes it. ds_ws == null: workspace-free, dkv keeps dS to itself and
 // dq recomputes it (no ordering dependency between the two kernels).
@@ -1082,12 +1453,27 @@ static void attn_bwd_launch(const void* do_, const void* q, const void* k,
                             long long dvstride, hipStream_t stream) {
   const unsigned grid = (unsigned)(S / 128) * (unsigned)(B * H);
   const int sched = attn_sched_get();
-  const int lds_dkv = 4 * 32 * D * 2 + 4 * 32 * D * 2 + 4 * 32 * 80;
+  const bool keylane = attn_dkv_get() == ATTN_DKV_KEYLANE;
+  // the dS workspace layout is private to the dkv/dq pair: the key-lane
+  // body publishes 2 KB tiles, the legacy body row-major
+  const int ws_tiled = keylane;
+  // K tiles + Q/dO images, then the row constants (key-lane) or the P/dS
+  // transpose buffer (legacy)
+  const int lds_dkv =
+      4 * 32 * D * 2 + 4 * 32 * D * 2 + (keylane ? 2 * 64 * 4 : 4 * 32 * 80);
+#define DKV_ARGS                                                              \
+  (const short*)do_, (const short*)q, (const short*)k, (const short*)v, lse,  \
+      delta_ws, dk, dv, (short*)ds_ws, B, S, H, KVH, scale, vstride,          \
+      dvstride, sched
 #define DKV_LAUNCH(OUT, PUB)                                                  \
-  attn_bwd_dkv_kernel<D, OUT, PUB><<<grid, 256, lds_dkv, stream>>>(           \
-      (const short*)do_, (const short*)q, (const short*)k, (const short*)v,   \
-      lse, delta_ws, dk, dv, (short*)ds_ws, B, S, H, KVH, scale, vstride,     \
-      dvstride, sched)
+  do {                                                                        \
+    if (keylane)                                                              \
+      attn_bwd_dkv_keylane_kernel<D, OUT, PUB>                                \
+          <<<grid, 256, lds_dkv, stream>>>(DKV_ARGS, ws_tiled);               \
+    else                                                                      \
+      attn_bwd_dkv_kernel<D, OUT, PUB>                                        \
+          <<<grid, 256, lds_dkv, stream>>>(DKV_ARGS);                         \
+  } while (0)
   if (ds_ws) {
     // dkv FIRST: it publishes the dS workspace the dq kernel consumes
     if (out_bf16)
@@ -1096,7 +1482,8 @@ static void attn_bwd_launch(const void* do_, const void* q, const void* k,
       DKV_LAUNCH(false, true);
     const int lds_dq = 2 * (32 * D * 2 + 32 * 128 * 2);
     attn_bwd_dq_kernel<D><<<grid, 256, lds_dq, stream>>>(
-        (const short*)k, (const short*)ds_ws, (short*)dq, B, S, H, KVH, sched);
+        (const short*)k, (const short*)ds_ws, (short*)dq, B, S, H, KVH, sched,
+        ws_tiled);
   } else {
     if (out_bf16)
       DKV_LAUNCH(true, false);
@@ -1108,6 +1495,7 @@ static void attn_bwd_launch(const void* do_, const void* q, const void* k,
         lse, delta_ws, (short*)dq, B, S, H, KVH, scale, vstride, sched);
   }
 #undef DKV_LAUNCH
+#undef DKV_ARGS
 }
 
 extern "C" {
@@ -1123,6 +1511,13 @@ long long attn_bwd_ws_limit(long long bytes) {
 int attn_sched_mode(int mode) {
   const int prev = attn_sched_get();
   if (mode >= 0) g_attn_sched = mode;
+  return prev;
+}
+
+// mode < 0: query only. Returns the mode in force before the call.
+int attn_dkv_mode(int mode) {
+  const int prev = attn_dkv_get();
+  if (mode >= 0) g_attn_dkv = mode;
   return prev;
 }
 

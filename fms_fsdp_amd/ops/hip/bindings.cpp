@@ -37,6 +37,7 @@ void launch_attn_bwd(const void*, const void*, const void*, const void*,
                      void*, int, int, int, int, int, float, int,
                      long long, long long, hipStream_t);
 int attn_sched_mode(int);
+int attn_dkv_mode(int);
 long long attn_bwd_ws_limit(long long);
 void launch_cconv_fwd(const void*, const void*, const float*, void*, int,
                       int, int, int, hipStream_t);
@@ -252,6 +253,20 @@ std::string attn_sched_mode_py(c10::optional<std::string> mode) {
     m = (*mode == "legacy") ? 1 : 0;
   }
   return attn_sched_mode(m) == 1 ? "legacy" : "balanced";
+}
+
+// Get/set the dk/dv kernel body of the attention backward ("keylane" |
+// "legacy", attention.hip). Returns the mode in force before the call,
+// so one process can A/B both bodies.
+std::string attn_dkv_mode_py(c10::optional<std::string> mode) {
+  int m = -1;
+  if (mode.has_value()) {
+    TORCH_CHECK(*mode == "keylane" || *mode == "legacy",
+                "attn_dkv_mode: expected 'keylane' or 'legacy', got '", *mode,
+                "'");
+    m = (*mode == "legacy") ? 1 : 0;
+  }
+  return attn_dkv_mode(m) == 1 ? "legacy" : "keylane";
 }
 
 // Get/set the largest dS workspace attn_bwd may allocate, in bytes
@@ -561,6 +576,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("attn_fwd", &attn_fwd);
   mod.def("attn_bwd", &attn_bwd);
   mod.def("attn_sched_mode", &attn_sched_mode_py,
+          pybind11::arg("mode") = pybind11::none());
+  mod.def("attn_dkv_mode", &attn_dkv_mode_py,
           pybind11::arg("mode") = pybind11::none());
   mod.def("attn_bwd_ws_limit", &attn_bwd_ws_limit_py,
           pybind11::arg("bytes") = pybind11::none());
