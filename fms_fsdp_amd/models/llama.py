@@ -139,7 +139,9 @@ class Attention(nn.Module):
             return out if residual is None else out + residual
         return ops.linear_flat(o2.view(b, s, -1), self.proj.weight, residual)
 
-    def forward(self, x, cos, sin, cache=None, residual=None):
+    def forward(self, x, cos, sin, cache=None, residual=None, doc_mask=None):
+        """doc_mask (ops.DocMask): attention stays inside each document of a
+        packed row. The KV-cache decode path ignores it."""
         b, s, _ = x.shape
         if getattr(self, "_disable_fused_residual", False):
             qkv = self.qkv(x)
@@ -154,7 +156,8 @@ class Attention(nn.Module):
             # straight from the fused projection; backward fills one
             # fused dqkv buffer (no cat/copies)
             o = ops.qkv_rope_attention(qkv, cos, sin, self.nheads,
-                                       self.kvheads, self.head_dim)
+                                       self.kvheads, self.head_dim,
+                                       doc_mask=doc_mask)
             return self._project_out(o.reshape(b, s, -1), residual, b, s)
         q, k, v = qkv.split(
             [self.nheads * self.head_dim,
@@ -177,7 +180,7 @@ class Attention(nn.Module):
                 is_causal=(s == k.shape[1]),
                 enable_gqa=(self.kvheads != self.nheads)).transpose(1, 2)
         else:
-            o = ops.attention_causal(q, k, v)      # (b, s, nheads, head_dim)
+            o = ops.attention_causal(q, k, v, doc_mask=doc_mask)   # (b,s,h,d)
         return self._project_out(o.reshape(b, s, -1), residual, b, s)
 
     def reset_parameters(self):
@@ -220,16 +223,18 @@ class LlamaBlock(nn.Module):
         self.mlp_norm = RMSNorm(cfg.emb_dim, cfg.norm_eps)
         self.mlp = SwiGLU(cfg)
 
-    def forward(self, x, cos, sin, cache=None):
+    def forward(self, x, cos, sin, cache=None, doc_mask=None):
         if cache is None and getattr(self, "_ac_enabled", False) \
                 and torch.is_grad_enabled():
             return torch.utils.checkpoint.checkpoint(
-                self._forward_impl, x, cos, sin, use_reentrant=False)
-        return self._forward_impl(x, cos, sin, cache)
+                self._forward_impl, x, cos, sin, None, doc_mask,
+                use_reentrant=False)
+        return self._forward_impl(x, cos, sin, cache, doc_mask)
 
-    def _forward_impl(self, x, cos, sin, cache=None):
+    def _forward_impl(self, x, cos, sin, cache=None, doc_mask=None):
         # both residual adds ride the projection GEMM epilogues (addmm)
-        h = self.attn(self.attn_norm(x), cos, sin, cache, residual=x)
+        h = self.attn(self.attn_norm(x), cos, sin, cache, residual=x,
+                      doc_mask=doc_mask)
         return self.mlp(self.mlp_norm(h), residual=h)
 
     def reset_parameters(self):
@@ -246,18 +251,27 @@ class Llama(nn.Module):
         self.layers = nn.ModuleList([LlamaBlock(cfg) for _ in range(cfg.nlayers)])
         self.norm = RMSNorm(cfg.emb_dim, cfg.norm_eps)
         self.lm_head = nn.Linear(cfg.emb_dim, cfg.src_vocab_size, bias=False)
+        # token id that ends a document in packed rows; when set, forward()
+        # masks attention at document boundaries (config knob `doc_mask`)
+        self.doc_mask_token = None
 
-    def forward(self, tokens, labels=None, include_embeds=False):
+    def forward(self, tokens, labels=None, include_embeds=False,
+                doc_mask=None):
         """tokens (b, s) int64 -> logits (b, s, V); with labels also the
         mean CE loss via the chunked fused kernel (never materializes the
         fp32 softmax — SURVEY.md hard-part 6). include_embeds additionally
         returns the final hidden states (speculator training input,
-        reference analog: EmbedLLaMA, train_speculator_utils.py:430-466)."""
+        reference analog: EmbedLLaMA, train_speculator_utils.py:430-466).
+        doc_mask (ops.DocMask) keeps attention inside each document of a
+        packed row; with `doc_mask_token` set it is built from `tokens`,
+        once, and shared by all layers. RoPE positions are not reset."""
         b, s = tokens.shape
+        if doc_mask is None and self.doc_mask_token is not None:
+            doc_mask = ops.doc_mask_from_tokens(tokens, self.doc_mask_token)
         x = self.embedding(tokens)
         cos, sin = self.rot_emb.get(s, x.device)
         for layer in self.layers:
-            x = layer(x, cos, sin)
+            x = layer(x, cos, sin, doc_mask=doc_mask)
         x = self.norm(x)
         if labels is not None:
             loss = ops.linear_cross_entropy(x, self.lm_head.weight, labels)

@@ -8,6 +8,7 @@ ops raise RuntimeError rather than silently falling back to eager
 """
 
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -226,10 +227,62 @@ def linear_flat(x, weight, residual=None):
 # --------------------------------------------------------------------------
 # Causal flash attention (MFMA tiled, GQA)
 # --------------------------------------------------------------------------
+class DocMask(NamedTuple):
+    """Document boundaries of packed rows, two int32 (b, s) tensors that
+    describe one mask from either side: query i sees key j iff
+    start[b, i] <= j <= i, equivalently j <= i < end[b, j].
+
+    start[b, i] is the position of the first token of i's document
+    (0 <= start <= i, non-decreasing); end[b, j] is the start of the next
+    document after j's, or s for the last one. Build it once per model
+    forward and share it between the layers."""
+    start: torch.Tensor
+    end: torch.Tensor
+
+
+def doc_mask_from_starts(doc_start):
+    """DocMask from the (b, s) first-position-of-my-document array. Pure
+    tensor ops, no host sync; CPU or GPU."""
+    b, s = doc_start.shape
+    start = doc_start.long()
+    pos = torch.arange(s, device=start.device).expand(b, s)
+    # position i opens a document iff start[i] == i; end[j] is the first
+    # such i > j: a reversed running minimum, shifted by one
+    opens = torch.where(start == pos, pos, torch.full_like(pos, s))
+    nxt = torch.cat([opens[:, 1:], torch.full_like(pos[:, :1], s)], dim=1)
+    end = torch.cummin(nxt.flip(1), dim=1).values.flip(1)
+    return DocMask(start.int().contiguous(), end.int().contiguous())
+
+
+def doc_mask_from_tokens(tokens, eos_token):
+    """DocMask of (b, s) token rows packed back to back, every document
+    ending in eos_token (the eos belongs to the document it ends):
+    start[i] = 1 + max{j < i : tokens[j] == eos}, or 0."""
+    b, s = tokens.shape
+    pos = torch.arange(s, device=tokens.device).expand(b, s)
+    after = torch.where(tokens == eos_token, pos + 1, torch.zeros_like(pos))
+    prev = torch.cat([torch.zeros_like(after[:, :1]), after[:, :-1]], dim=1)
+    return doc_mask_from_starts(torch.cummax(prev, dim=1).values)
+
+
+def _pad_doc_mask(doc_mask, s_pad):
+    """Pad rows form a document of their own behind the real ones: start =
+    s, end = s_pad. Real keys keep end <= s, so pad queries see none."""
+    b, s = doc_mask.start.shape
+    if s == s_pad:
+        return doc_mask.start.contiguous(), doc_mask.end.contiguous()
+    start = doc_mask.start.new_full((b, s_pad), s)
+    end = doc_mask.end.new_full((b, s_pad), s_pad)
+    start[:, :s] = doc_mask.start
+    end[:, :s] = doc_mask.end
+    return start, end
+
+
 class _FlashAttnFn(torch.autograd.Function):
     """Kernel operates on seq multiples of 128; arbitrary lengths are
     zero-padded at the END (causality keeps pad keys invisible to real
-    queries) and sliced back."""
+    queries) and sliced back. With doc_start/doc_end (a DocMask's two
+    arrays, already padded) the document-masked kernels run."""
 
     @staticmethod
     def _pad(t, s_pad):
@@ -241,27 +294,34 @@ class _FlashAttnFn(torch.autograd.Function):
         return out
 
     @staticmethod
-    def forward(ctx, q, k, v):
+    def forward(ctx, q, k, v, doc_start=None, doc_end=None):
         ext = _require_ext("attention")
         s = q.shape[1]
         s_pad = (s + 127) // 128 * 128
         qp = _FlashAttnFn._pad(q, s_pad)
         kp = _FlashAttnFn._pad(k, s_pad)
         vp = _FlashAttnFn._pad(v, s_pad)
-        o, lse = ext.attn_fwd(qp, kp, vp)
-        ctx.save_for_backward(qp, kp, vp, o, lse)
+        if doc_start is None:
+            o, lse = ext.attn_fwd(qp, kp, vp)
+            ctx.save_for_backward(qp, kp, vp, o, lse)
+        else:
+            o, lse = ext.attn_fwd_doc(qp, kp, vp, doc_start)
+            ctx.save_for_backward(qp, kp, vp, o, lse, doc_start, doc_end)
         ctx.s = s
         return o[:, :s] if s != s_pad else o
 
     @staticmethod
     def backward(ctx, do):
-        qp, kp, vp, o, lse = ctx.saved_tensors
+        qp, kp, vp, o, lse, *doc = ctx.saved_tensors
         s, s_pad = ctx.s, qp.shape[1]
         dop = _FlashAttnFn._pad(do, s_pad)
-        dq, dk, dv = _C.attn_bwd(dop, qp, kp, vp, o, lse, None)
+        if doc:
+            dq, dk, dv = _C.attn_bwd_doc(dop, qp, kp, vp, o, lse, None, *doc)
+        else:
+            dq, dk, dv = _C.attn_bwd(dop, qp, kp, vp, o, lse, None)
         if s != s_pad:
             dq, dk, dv = dq[:, :s], dk[:, :s], dv[:, :s]
-        return dq, dk, dv
+        return dq, dk, dv, None, None
 
 
 class _QKVRopeAttnFn(torch.autograd.Function):
@@ -278,7 +338,8 @@ class _QKVRopeAttnFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, nheads, kvheads, head_dim):
+    def forward(ctx, qkv, cos, sin, nheads, kvheads, head_dim,
+                doc_start=None, doc_end=None):
         ext = _require_ext("attention")
         b, s, _ = qkv.shape
         d = head_dim
@@ -289,14 +350,19 @@ class _QKVRopeAttnFn(torch.autograd.Function):
         cos = cos.float().contiguous()
         sin = sin.float().contiguous()
         qr, kr = ext.rope_fwd(q, k, cos, sin, False)   # strided reads
-        o, lse = ext.attn_fwd(qr, kr, v)               # strided v
-        ctx.save_for_backward(qkv, qr, kr, o, lse, cos, sin)
+        if doc_start is None:
+            o, lse = ext.attn_fwd(qr, kr, v)           # strided v
+            ctx.save_for_backward(qkv, qr, kr, o, lse, cos, sin)
+        else:
+            o, lse = ext.attn_fwd_doc(qr, kr, v, doc_start)
+            ctx.save_for_backward(qkv, qr, kr, o, lse, cos, sin, doc_start,
+                                  doc_end)
         ctx.dims = (nheads, kvheads, d)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, qr, kr, o, lse, cos, sin = ctx.saved_tensors
+        qkv, qr, kr, o, lse, cos, sin, *doc = ctx.saved_tensors
         nheads, kvheads, d = ctx.dims
         b, s, _ = qkv.shape
         hq, hk = nheads * d, kvheads * d
@@ -305,45 +371,57 @@ class _QKVRopeAttnFn(torch.autograd.Function):
         dq_sl = dqkv[..., :hq].view(b, s, nheads, d)
         dk_sl = dqkv[..., hq:hq + hk].view(b, s, kvheads, d)
         dv_sl = dqkv[..., hq + hk:].view(b, s, kvheads, d)
+        # document-masked calls differ in the attention kernels only
+        bwd = ((lambda *a: _C.attn_bwd_doc(*a, *doc)) if doc
+               else _C.attn_bwd)
         if nheads == kvheads:
             # dv written straight into the fused buffer by the kernel
-            dq, dk, _ = _C.attn_bwd(do.contiguous(), qr, kr, v, o, lse,
-                                    dv_sl)
+            dq, dk, _ = bwd(do.contiguous(), qr, kr, v, o, lse, dv_sl)
         else:
-            dq, dk, dv = _C.attn_bwd(do.contiguous(), qr, kr, v, o, lse,
-                                     None)
+            dq, dk, dv = bwd(do.contiguous(), qr, kr, v, o, lse, None)
             dv_sl.copy_(dv)
         # inverse rotation scattered into the fused buffer slices
         _C.rope_into(dq, dq_sl, cos, sin, True)
         _C.rope_into(dk, dk_sl, cos, sin, True)
-        return dqkv, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
-def qkv_rope_attention(qkv, cos, sin, nheads, kvheads, head_dim):
+def qkv_rope_attention(qkv, cos, sin, nheads, kvheads, head_dim,
+                       doc_mask=None):
     """Fused GPU path; callers gate on seq%128==0 and head_dim in
     (64, 128) and fall back to the modular split+rope+attention path
-    otherwise (decode/KV-cache, odd lengths, CPU)."""
+    otherwise (decode/KV-cache, odd lengths, CPU). doc_mask (DocMask)
+    keeps attention inside each document."""
+    doc = () if doc_mask is None else (doc_mask.start.contiguous(),
+                                       doc_mask.end.contiguous())
     if qkv.dtype == torch.float16:
         return _QKVRopeAttnFn.apply(qkv.bfloat16(), cos, sin, nheads,
-                                    kvheads, head_dim).half()
-    return _QKVRopeAttnFn.apply(qkv, cos, sin, nheads, kvheads, head_dim)
+                                    kvheads, head_dim, *doc).half()
+    return _QKVRopeAttnFn.apply(qkv, cos, sin, nheads, kvheads, head_dim,
+                                *doc)
 
 
-def attention_causal(q, k, v):
+def attention_causal(q, k, v, doc_mask=None):
+    """Causal attention, q (b,s,h,d), k/v (b,s,kvh,d). doc_mask (DocMask)
+    additionally keeps every query inside its own document."""
     if q.is_cuda:
         if os.environ.get("FMS_AMD_ALLOW_TORCH_SDPA") == "1":
+            if doc_mask is not None:
+                return reference.attention_causal(q, k, v, doc_mask)
             import torch.nn.functional as F
             o = F.scaled_dot_product_attention(
                 q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
                 is_causal=True, enable_gqa=(k.shape[2] != q.shape[2]))
             return o.transpose(1, 2)
+        if q.dtype == torch.float32:
+            return reference.attention_causal(q, k, v, doc_mask)
+        doc = () if doc_mask is None else _pad_doc_mask(
+            doc_mask, (q.shape[1] + 127) // 128 * 128)
         if q.dtype == torch.float16:
             return _FlashAttnFn.apply(q.bfloat16(), k.bfloat16(),
-                                      v.bfloat16()).half()
-        if q.dtype == torch.float32:
-            return reference.attention_causal(q, k, v)
-        return _FlashAttnFn.apply(q, k, v)
-    return reference.attention_causal(q, k, v)
+                                      v.bfloat16(), *doc).half()
+        return _FlashAttnFn.apply(q, k, v, *doc)
+    return reference.attention_causal(q, k, v, doc_mask)
 
 
 def attn_bwd_workspace_limit(mb=None):

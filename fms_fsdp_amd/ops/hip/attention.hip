@@ -166,18 +166,30 @@ __device__ __forceinline__ unsigned tr_base(int lane, int col, int hb) {
                     (col >> 4) * R4B);
 }
 
+// document-mask arrays are clamped where they are read (DOCMASK kernels)
+__device__ __forceinline__ int doc_clamp(int v, int lo, int hi) {
+  return min(max(v, lo), hi);
+}
 
 // ---------------------------------------------------------------------
 // Forward. Block = 4 waves x 32 q-rows = 128 q rows; KV tile = 64 keys.
 // 1-D grid of (s/128)*(b*h) workgroups; attn_sched_map() (attn_sched.h)
 // turns the linear id into (q tile, bh).
+//
+// DOCMASK: query i sees key j iff docs[b][i] <= j <= i, docs = the (b, s)
+// int32 position of the first token of i's document (non-decreasing). Each
+// lane holds its row's start (clamped into [0, q], so no content of the
+// array can move a loop bound or an address out of range); the KV loop
+// starts at the tile of docs[q0], the workgroup's minimum; the wave-uniform
+// flags take the wave's own first and last start, so tiles strictly inside
+// one document run the unmasked instruction stream.
 // ---------------------------------------------------------------------
-template <int D>
+template <int D, bool DOCMASK = false>
 __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
     const short* __restrict__ qg, const short* __restrict__ kg,
     const short* __restrict__ vg, short* __restrict__ og,
     float* __restrict__ lseg, int B, int S, int H, int KVH, float scale,
-    long long vstride, int sched) {
+    long long vstride, int sched, const int* __restrict__ docs = nullptr) {
   constexpr int KVB = 64;
   constexpr int NC = D / 16;   // QK^T k-chunks
   constexpr int NT = D / 32;   // 32-wide output tiles
@@ -214,6 +226,18 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
   const short* kbase = kg + ((long long)b * S * KVH + (long long)kvh) * D;
   // v may be a strided view (a slice of the fused qkv projection)
   const short* vbase = vg + (long long)b * S * vstride + (long long)kvh * D;
+
+  // document mask: this lane's first visible key, the first and last
+  // start of the wave (wave-uniform) and the first KV tile of the block
+  int my_start = 0, w_lo = 0, w_hi = 0, tile0 = 0;
+  if constexpr (DOCMASK) {
+    const int* dsp = docs + (long long)b * S;
+    my_start = doc_clamp(dsp[my_q], 0, my_q);
+    w_lo = __builtin_amdgcn_readfirstlane(doc_clamp(dsp[qw], 0, qw));
+    w_hi = __builtin_amdgcn_readfirstlane(
+        doc_clamp(dsp[qw + 31], 0, qw + 31));
+    tile0 = __builtin_amdgcn_readfirstlane(doc_clamp(dsp[q0], 0, q0)) / 64;
+  }
 
   // softmax runs in base 2 (v_exp_f32 is natively 2^x; folding log2(e)
   // into the scale drops one v_mul per exponential)
@@ -252,6 +276,10 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
   const short* vp_s = vbase + (long long)skey * vstride + sd0;
   const long long kstep = (long long)KVB * krow_stride;
   const long long vstep = (long long)KVB * vstride;
+  if constexpr (DOCMASK) {   // tiles in front of the block's first document
+    kp_s += tile0 * kstep;
+    vp_s += tile0 * vstep;
+  }
   int soff[D / 64][2];
 #pragma unroll
   for (int c2 = 0; c2 < D / 64; ++c2) {
@@ -282,7 +310,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
   const unsigned pvb[2] = {(unsigned)(unsigned long long)VLDS(0) + pv_swz,
                            (unsigned)(unsigned long long)VLDS(1) + pv_swz};
   int cur = 0;
-  for (int tile = 0; tile < ntiles; ++tile) {
+  for (int tile = tile0; tile < ntiles; ++tile) {
     const int kv0 = tile * KVB;
     if (tile + 1 < ntiles) stage_v(cur ^ 1);
 
@@ -296,10 +324,14 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
     // S-phase + softmax + pack for one sub-tile; PV split out so kt=1's
     // PV can run after the mid-tile K barrier (single-buffered K).
     bf16x8v pb1_0, pb1_1;
-    const bool act1 = (kv0 + 32) <= qw + 31;   // wave-uniform causal
+    // wave-uniform: causal, and (DOCMASK) not wholly in front of the
+    // wave's first document
+    const bool act1 = (kv0 + 32) <= qw + 31 && (!DOCMASK || kv0 + 63 >= w_lo);
+    const bool act0 = !DOCMASK || kv0 + 31 >= w_lo;
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
       const int kv32 = kv0 + kt * 32;
+      if (kt == 0 && !act0) continue;
       if (kt == 1 && !act1) break;
       f32x16 accS = (f32x16)(0.f);
 #pragma unroll
@@ -310,12 +342,16 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
         accS = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qb[c], accS, 0, 0, 0);
       }
       float p[16];
-      const bool partial = (kv32 + 32) > (qw + 1);
+      // DOCMASK: the lower mask is needed up to the wave's last start
+      const bool partial =
+          (kv32 + 32) > (qw + 1) || (DOCMASK && kv32 < w_hi);
       float mt = -1e30f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float sv = accS[r];                   // q pre-scaled at load
-        if (partial && (kv32 + DROW(r, hb)) > my_q) sv = -1e30f;
+        const int key = kv32 + DROW(r, hb);
+        if (partial && (key > my_q || (DOCMASK && key < my_start)))
+          sv = -1e30f;
         p[r] = sv;
         mt = fmaxf(mt, sv);
       }
@@ -333,6 +369,12 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         p[r] = exp2f(p[r] - m_run);
+        if constexpr (DOCMASK) {
+          // a row whose document starts behind this sub-tile still has
+          // m_run = -1e30: exp2(-1e30 - m_run) would be 1, not 0
+          const int key = kv32 + DROW(r, hb);
+          if (partial && (key > my_q || key < my_start)) p[r] = 0.f;
+        }
         s_own += p[r];
       }
       l_run = l_run * alpha + s_own + __shfl_xor(s_own, 32, 64);
@@ -623,13 +665,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(
 // backward instead of 5); selected only when the (b*h, s, s) workspace
 // would exceed the limit (attn_ws.h).
 // ---------------------------------------------------------------------
-template <int D>
+// DOCMASK as in the forward (docs = first position of the row's document):
+// per-lane start, key sweep from the 32-key tile of docs[q0], wave flags
+// from the wave's first and last start.
+template <int D, bool DOCMASK = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_recompute_kernel(
     const short* __restrict__ dog, const short* __restrict__ qg,
     const short* __restrict__ kg, const short* __restrict__ vg,
     const float* __restrict__ lseg, const float* __restrict__ deltag,
     short* __restrict__ dqg, int B, int S, int H, int KVH, float scale,
-    long long vstride, int sched) {
+    long long vstride, int sched, const int* __restrict__ docs = nullptr) {
   constexpr int KVB = 32;
   constexpr int NC = D / 16;
   constexpr int NT = D / 32;
@@ -671,6 +716,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_recompute_kernel(
   const float delta_q = deltag[(long long)bh * S + my_q];
   const float scale2 = scale * 1.4426950408889634f;
 
+  int my_start = 0, w_lo = 0, w_hi = 0, tile0 = 0;
+  if constexpr (DOCMASK) {
+    const int* dsp = docs + (long long)b * S;
+    my_start = doc_clamp(dsp[my_q], 0, my_q);
+    w_lo = __builtin_amdgcn_readfirstlane(doc_clamp(dsp[qw], 0, qw));
+    w_hi = __builtin_amdgcn_readfirstlane(
+        doc_clamp(dsp[qw + 31], 0, qw + 31));
+    tile0 = __builtin_amdgcn_readfirstlane(doc_clamp(dsp[q0], 0, q0)) / 32;
+  }
+
   f32x16 accDQ[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) accDQ[t] = (f32x16)(0.f);
@@ -686,6 +741,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_recompute_kernel(
   const short* vp_s = vbase + (long long)skey * vstride + skd0;
   const long long kstep = (long long)KVB * krow_stride;
   const long long vstep = (long long)KVB * vstride;
+  if constexpr (DOCMASK) {   // tiles in front of the block's first document
+    kp_s += tile0 * kstep;
+    vp_s += tile0 * vstep;
+  }
   const int soff0 = SUBT_OFF(skey, skd0, 8);
   const int soff1 = SUBT_OFF(skey, skd0 + 8, 8);   // D = 128 only
   f32x4v kpre0, kpre1, vpre0, vpre1;
@@ -718,13 +777,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_recompute_kernel(
                            (unsigned)(unsigned long long)KIMG(1) + ktr};
 
   int cur = 0;
-  for (int tile = 0; tile < ntiles; ++tile) {
+  for (int tile = tile0; tile < ntiles; ++tile) {
     const int kv0 = tile * KVB;
     const bool more = tile + 1 < ntiles;
     if (more) DQR_FETCH();
     // wave-uniform causal skip: key tiles past this wave's last q row
-    // contribute exactly zero (the wave still stages and syncs)
-    if (kv0 <= qw + 31) {
+    // (DOCMASK: or wholly in front of its first document) contribute
+    // exactly zero (the wave still stages and syncs)
+    if (kv0 <= qw + 31 && (!DOCMASK || kv0 + 31 >= w_lo)) {
       f32x16 accS = (f32x16)(0.f), accDP = (f32x16)(0.f);
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
@@ -739,12 +799,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_recompute_kernel(
       const unsigned kbase_t = kib[cur];
       U2x64 fr[2][2];
       tr_issue4<0, 128, 512, 640>(kbase_t, fr[0][0], fr[0][1]);
-      const bool partial = (kv0 + 31) > qw;
+      const bool partial = (kv0 + 31) > qw || (DOCMASK && kv0 < w_hi);
       float ds[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
+        // select, never multiply: exp2 of a masked key may be inf
         float pval = exp2f(accS[r] * scale2 - lse_q2);
-        if (partial && (kv0 + DROW(r, hb)) > my_q) pval = 0.f;
+        const int key = kv0 + DROW(r, hb);
+        if (partial && (key > my_q || (DOCMASK && key < my_start)))
+          pval = 0.f;
         ds[r] = pval * (accDP[r] - delta_q) * scale;
       }
       // dS^T -> B-operand in registers (two 16-key chunks)
@@ -1106,7 +1169,13 @@ __device__ __forceinline__ bf16x8v pack_slice(const float* p) {
   return b.v;
 }
 
-template <int D, bool OUT_BF16, bool PUBLISH_DS>
+//
+// DOCMASK (never with PUBLISH_DS): doce = (b, s) int32 start of the next
+// document after the key's (s for the last); query i sees key j iff
+// j <= i < doce[j]. Each lane holds its key's end, clamped into
+// [key + 1, S]; the q loop stops at the end of the block's last key
+// rounded up to 32, which is the block's maximum and workgroup-uniform.
+template <int D, bool OUT_BF16, bool PUBLISH_DS, bool DOCMASK = false>
 __global__ __launch_bounds__(256, D == 64 ? 3 : 2) void
 attn_bwd_dkv_keylane_kernel(
     const short* __restrict__ dog, const short* __restrict__ qg,
@@ -1115,7 +1184,8 @@ attn_bwd_dkv_keylane_kernel(
     void* __restrict__ dkg, void* __restrict__ dvg,
     short* __restrict__ dsw, int B, int S, int H,
     int KVH, float scale, long long vstride, long long dvstride, int sched,
-    int ws_tiled) {
+    int ws_tiled, const int* __restrict__ doce = nullptr) {
+  static_assert(!(DOCMASK && PUBLISH_DS), "masked backward is workspace-free");
   constexpr int KVB = 32;   // keys per wave; block = 4 waves = 128 keys
   constexpr int NC = D / 16;
   constexpr int NT = D / 32;
@@ -1237,6 +1307,15 @@ attn_bwd_dkv_keylane_kernel(
   const unsigned tr1 = tr0 ^ 16u;
   const float scale2 = scale * 1.4426950408889634f;
   const int key = kv0 + col;
+  int my_end = S, q_end = S;
+  if constexpr (DOCMASK) {
+    const int* dep = doce + (long long)b * S;
+    my_end = doc_clamp(dep[key], key + 1, S);
+    const int klast = tile * 128 + 127;
+    const int e = __builtin_amdgcn_readfirstlane(
+        doc_clamp(dep[klast], klast + 1, S));
+    q_end = min(S, (e + 31) & ~31);
+  }
   // dS workspace address = uniform base + q0 * pub_qmul + lane part; the
   // second slice sits pub_kc elements on. Row-major [bh][key][q]: lane
   // (key, hb) stores q 16kc + 8hb .. +7 of its key row. Tiled
@@ -1251,8 +1330,8 @@ attn_bwd_dkv_keylane_kernel(
       (ws_tiled ? (long long)(kv0 / 32) * S * 32 : (long long)kv0 * S);
 
   int cur = 0;
-  for (int q0 = q_start; q0 < S; q0 += 32) {
-    const bool more = q0 + 32 < S;
+  for (int q0 = q_start; q0 < q_end; q0 += 32) {
+    const bool more = q0 + 32 < q_end;
 
     f32x16 accS = (f32x16)(0.f), accDP = (f32x16)(0.f);
 #pragma unroll
@@ -1281,7 +1360,7 @@ attn_bwd_dkv_keylane_kernel(
         const int r = g * 4 + j;
         const int q = q0 + DROW(r, hb);
         float pval = exp2f(accS[r] * scale2 - lse_q2[j]);
-        if (key > q) pval = 0.f;
+        if (key > q || (DOCMASK && q >= my_end)) pval = 0.f;
         pv[r] = pval;
         ds[r] = pval * (accDP[r] - delta_q[j]) * scale;
       }
@@ -1498,6 +1577,38 @@ static void attn_bwd_launch(const void* do_, const void* q, const void* k,
 #undef DKV_ARGS
 }
 
+// Document-masked backward: always workspace-free (skipped tiles would
+// leave a workspace unwritten) and always the key-lane dkv body; the dkv
+// mode and the workspace limit govern unmasked calls only.
+template <int D>
+static void attn_bwd_doc_launch(const void* do_, const void* q, const void* k,
+                                const void* v, const float* lse, void* dq,
+                                void* dk, void* dv, float* delta_ws,
+                                const int* doc_start, const int* doc_end,
+                                int B, int S, int H, int KVH, float scale,
+                                int out_bf16, long long vstride,
+                                long long dvstride, hipStream_t stream) {
+  const unsigned grid = (unsigned)(S / 128) * (unsigned)(B * H);
+  const int sched = attn_sched_get();
+  const int lds_dkv = 4 * 32 * D * 2 + 4 * 32 * D * 2 + 2 * 64 * 4;
+#define DKV_DOC_LAUNCH(OUT)                                                   \
+  attn_bwd_dkv_keylane_kernel<D, OUT, false, true>                            \
+      <<<grid, 256, lds_dkv, stream>>>(                                       \
+          (const short*)do_, (const short*)q, (const short*)k,                \
+          (const short*)v, lse, delta_ws, dk, dv, (short*)nullptr, B, S, H,   \
+          KVH, scale, vstride, dvstride, sched, 0, doc_end)
+  if (out_bf16)
+    DKV_DOC_LAUNCH(true);
+  else
+    DKV_DOC_LAUNCH(false);
+#undef DKV_DOC_LAUNCH
+  const int lds_dq = 2 * (32 * D * 2 + 32 * D * 2);   // dbuf K + V images
+  attn_bwd_dq_recompute_kernel<D, true><<<grid, 256, lds_dq, stream>>>(
+      (const short*)do_, (const short*)q, (const short*)k, (const short*)v,
+      lse, delta_ws, (short*)dq, B, S, H, KVH, scale, vstride, sched,
+      doc_start);
+}
+
 extern "C" {
 
 // bytes < 0: query only. Returns the limit in force before the call.
@@ -1553,6 +1664,44 @@ void launch_attn_bwd(const void* do_, const void* q, const void* k,
   else
     attn_bwd_launch<64>(do_, q, k, v, lse, dq, dk, dv, delta_ws, ds_ws, B, S,
                         H, KVH, scale, out_bf16, vstride, dvstride, stream);
+}
+
+// doc_start / doc_end: (b, s) int32, see the DOCMASK kernel comments
+void launch_attn_fwd_doc(const void* q, const void* k, const void* v, void* o,
+                         float* lse, const int* doc_start, int B, int S,
+                         int H, int KVH, int D, float scale,
+                         long long vstride, hipStream_t stream) {
+  const unsigned grid = (unsigned)(S / 128) * (unsigned)(B * H);
+  const int sched = attn_sched_get();
+  const int lds = 3 * 64 * D * 2;  // single K image + dbuf V
+  if (D == 128)
+    attn_fwd_kernel<128, true><<<grid, 256, lds, stream>>>(
+        (const short*)q, (const short*)k, (const short*)v, (short*)o, lse, B,
+        S, H, KVH, scale, vstride, sched, doc_start);
+  else
+    attn_fwd_kernel<64, true><<<grid, 256, lds, stream>>>(
+        (const short*)q, (const short*)k, (const short*)v, (short*)o, lse, B,
+        S, H, KVH, scale, vstride, sched, doc_start);
+}
+
+void launch_attn_bwd_doc(const void* do_, const void* q, const void* k,
+                         const void* v, const void* o, const float* lse,
+                         void* dq, void* dk, void* dv, float* delta_ws,
+                         const int* doc_start, const int* doc_end, int B,
+                         int S, int H, int KVH, int D, float scale,
+                         int out_bf16, long long vstride, long long dvstride,
+                         hipStream_t stream) {
+  const long long rows = (long long)B * S * H;
+  attn_bwd_delta_kernel<<<(int)((rows * 64 + 255) / 256), 256, 0, stream>>>(
+      (const short*)do_, (const short*)o, delta_ws, D, S, H, rows);
+  if (D == 128)
+    attn_bwd_doc_launch<128>(do_, q, k, v, lse, dq, dk, dv, delta_ws,
+                             doc_start, doc_end, B, S, H, KVH, scale,
+                             out_bf16, vstride, dvstride, stream);
+  else
+    attn_bwd_doc_launch<64>(do_, q, k, v, lse, dq, dk, dv, delta_ws,
+                            doc_start, doc_end, B, S, H, KVH, scale,
+                            out_bf16, vstride, dvstride, stream);
 }
 
 }  // extern "C"

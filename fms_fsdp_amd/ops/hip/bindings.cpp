@@ -36,6 +36,13 @@ void launch_attn_bwd(const void*, const void*, const void*, const void*,
                      const void*, const float*, void*, void*, void*, float*,
                      void*, int, int, int, int, int, float, int,
                      long long, long long, hipStream_t);
+void launch_attn_fwd_doc(const void*, const void*, const void*, void*, float*,
+                         const int*, int, int, int, int, int, float,
+                         long long, hipStream_t);
+void launch_attn_bwd_doc(const void*, const void*, const void*, const void*,
+                         const void*, const float*, void*, void*, void*,
+                         float*, const int*, const int*, int, int, int, int,
+                         int, float, int, long long, long long, hipStream_t);
 int attn_sched_mode(int);
 int attn_dkv_mode(int);
 long long attn_bwd_ws_limit(long long);
@@ -342,6 +349,75 @@ std::tuple<Tensor, Tensor, Tensor> attn_bwd(Tensor do_, Tensor q, Tensor k,
   return {dq, dk.to(torch::kBFloat16), dv.to(torch::kBFloat16)};
 }
 
+// (b, s) int32 document boundaries of the masked attention kernels
+static void check_doc_array(const Tensor& t, const Tensor& q,
+                            const char* name) {
+  TORCH_CHECK(t.scalar_type() == torch::kInt32, name, " must be int32");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == q.size(0) && t.size(1) == q.size(1),
+              name, " must have shape (b, s)");
+  TORCH_CHECK(t.device() == q.device(), name, " must be on q's device");
+}
+
+// Document-masked causal attention: query i sees key j iff
+// doc_start[b, i] <= j <= i. Otherwise attn_fwd.
+std::tuple<Tensor, Tensor> attn_fwd_doc(Tensor q, Tensor k, Tensor v,
+                                        Tensor doc_start) {
+  CHECK_BF16_CONTIG(q);
+  CHECK_BF16_CONTIG(k);
+  const long long vs = row_stride4(v);  // strided (fused-qkv slice) ok
+  const int b = q.size(0), s = q.size(1), h = q.size(2), d = q.size(3);
+  const int kvh = k.size(2);
+  TORCH_CHECK(d == 64 || d == 128, "head_dim must be 64 or 128");
+  TORCH_CHECK(s % 128 == 0, "seq len must be a multiple of 128");
+  check_doc_array(doc_start, q, "doc_start");
+  auto o = torch::empty_like(q);
+  auto lse = torch::empty({b, h, s}, q.options().dtype(torch::kFloat32));
+  const float scale = 1.f / sqrtf((float)d);
+  launch_attn_fwd_doc(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+                      lse.data_ptr<float>(), doc_start.data_ptr<int>(), b, s,
+                      h, kvh, d, scale, vs, cur_stream());
+  return {o, lse};
+}
+
+// Backward of attn_fwd_doc. doc_end[b, j] = start of the document after
+// j's (s for the last): the same mask seen from the key. Always the
+// workspace-free kernels: no dS workspace is allocated at any limit.
+std::tuple<Tensor, Tensor, Tensor> attn_bwd_doc(
+    Tensor do_, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse,
+    c10::optional<Tensor> dv_out, Tensor doc_start, Tensor doc_end) {
+  CHECK_BF16_CONTIG(do_);
+  const long long vs = row_stride4(v);
+  const int b = q.size(0), s = q.size(1), h = q.size(2), d = q.size(3);
+  const int kvh = k.size(2);
+  check_doc_array(doc_start, q, "doc_start");
+  check_doc_array(doc_end, q, "doc_end");
+  auto dq = torch::empty_like(q);
+  const bool out_bf16 = (kvh == h);  // no GQA collisions: direct bf16
+  auto opts = q.options().dtype(out_bf16 ? torch::kBFloat16 : torch::kFloat32);
+  auto dk = out_bf16 ? torch::empty({b, s, kvh, d}, opts)
+                     : torch::zeros({b, s, kvh, d}, opts);
+  Tensor dv;
+  long long dvs = (long long)kvh * d;
+  if (dv_out.has_value() && out_bf16) {
+    dv = *dv_out;
+    dvs = row_stride4(dv);
+  } else {
+    dv = out_bf16 ? torch::empty({b, s, kvh, d}, opts)
+                  : torch::zeros({b, s, kvh, d}, opts);
+  }
+  auto delta = torch::empty({b, h, s}, q.options().dtype(torch::kFloat32));
+  const float scale = 1.f / sqrtf((float)d);
+  launch_attn_bwd_doc(do_.data_ptr(), q.data_ptr(), k.data_ptr(),
+                      v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+                      dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                      delta.data_ptr<float>(), doc_start.data_ptr<int>(),
+                      doc_end.data_ptr<int>(), b, s, h, kvh, d, scale,
+                      out_bf16 ? 1 : 0, vs, dvs, cur_stream());
+  if (out_bf16) return {dq, dk, dv};
+  return {dq, dk.to(torch::kBFloat16), dv.to(torch::kBFloat16)};
+}
+
 Tensor cconv_fwd(Tensor x, Tensor w, Tensor bias) {
   CHECK_BF16_CONTIG(x);
   CHECK_BF16_CONTIG(w);
@@ -575,6 +651,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ssd_ygate_bwd", &ssd_ygate_bwd);
   mod.def("attn_fwd", &attn_fwd);
   mod.def("attn_bwd", &attn_bwd);
+  mod.def("attn_fwd_doc", &attn_fwd_doc);
+  mod.def("attn_bwd_doc", &attn_bwd_doc);
   mod.def("attn_sched_mode", &attn_sched_mode_py,
           pybind11::arg("mode") = pybind11::none());
   mod.def("attn_dkv_mode", &attn_dkv_mode_py,

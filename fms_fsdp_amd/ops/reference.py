@@ -30,15 +30,30 @@ def rope_apply(q, k, cos, sin):
     return rot(q), rot(k)
 
 
-def attention_causal(q, k, v):
-    """q (b,s,h,d), k/v (b,s,kvh,d) -> (b,s,h,d). Causal, GQA broadcast."""
+def doc_mask_matrix(doc_start):
+    """(b, s) first position of each token's document -> (b, s, s) bool,
+    [b, i, j] = query i sees key j = doc_start[b, i] <= j <= i."""
+    s = doc_start.shape[1]
+    pos = torch.arange(s, device=doc_start.device)
+    return ((pos[None, None, :] <= pos[None, :, None])
+            & (pos[None, None, :] >= doc_start[:, :, None]))
+
+
+def attention_causal(q, k, v, doc_mask=None):
+    """q (b,s,h,d), k/v (b,s,kvh,d) -> (b,s,h,d). Causal, GQA broadcast.
+    doc_mask (ops.DocMask): attention stays inside each document."""
     b, s, h, d = q.shape
     kvh = k.shape[2]
     qt = q.transpose(1, 2).float()
     kt = k.transpose(1, 2).float()
     vt = v.transpose(1, 2).float()
-    o = F.scaled_dot_product_attention(qt, kt, vt, is_causal=True,
-                                       enable_gqa=(kvh != h))
+    if doc_mask is None:
+        o = F.scaled_dot_product_attention(qt, kt, vt, is_causal=True,
+                                           enable_gqa=(kvh != h))
+    else:
+        mask = doc_mask_matrix(doc_mask.start.to(q.device))[:, None]
+        o = F.scaled_dot_product_attention(qt, kt, vt, attn_mask=mask,
+                                           enable_gqa=(kvh != h))
     return o.transpose(1, 2).to(q.dtype)
 
 

@@ -88,6 +88,9 @@ def main(**kwargs):
     else:
         model = Llama(model_config)
         model.reset_parameters()
+    if cfg.doc_mask:
+        # documents are packed back to back, each ending in eos_token
+        model.doc_mask_token = cfg.eos_token
 
     if rank == 0:
         print(f"--> model has {model.param_count() / 1e6:.2f}M params")
