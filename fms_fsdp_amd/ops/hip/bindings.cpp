@@ -107,7 +107,20 @@ std::tuple<Tensor, Tensor> rmsnorm_bwd(Tensor dy, Tensor x, Tensor w,
                                        c10::optional<Tensor> dextra) {
   CHECK_BF16_CONTIG(dy);
   CHECK_BF16_CONTIG(x);
+  CHECK_BF16_CONTIG(w);
+  TORCH_CHECK(x.dim() == 2 && dy.sizes() == x.sizes(),
+              "dy and x must be (rows, H)");
   const int rows = x.size(0), H = x.size(1);
+  TORCH_CHECK(H % 8 == 0, "H must be divisible by 8");
+  TORCH_CHECK(w.numel() == H, "w must have H elements");
+  TORCH_CHECK(rinv.scalar_type() == torch::kFloat32 && rinv.is_contiguous() &&
+                  rinv.numel() == rows,
+              "rinv must be fp32 with one element per row");
+  if (dextra.has_value()) {
+    TORCH_CHECK(dextra->scalar_type() == torch::kBFloat16 &&
+                    dextra->is_contiguous() && dextra->sizes() == x.sizes(),
+                "dextra must have x's shape and dtype");
+  }
   auto dx = torch::empty_like(x);
   auto dw = torch::zeros({H}, x.options().dtype(torch::kFloat32));
   launch_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
@@ -201,7 +214,14 @@ void ce_fwd_bwd(Tensor logits, Tensor labels, Tensor loss_sum, Tensor denom,
                 int64_t ignore_index) {
   CHECK_BF16_CONTIG(logits);
   TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.is_contiguous());
+  TORCH_CHECK(logits.dim() == 2, "logits must be (rows, V)");
   const int rows = logits.size(0), V = logits.size(1);
+  // rows are read and written as 16-byte vectors
+  TORCH_CHECK(V % 8 == 0, "V must be divisible by 8");
+  TORCH_CHECK(labels.numel() == rows, "labels must have one entry per row");
+  TORCH_CHECK(loss_sum.scalar_type() == torch::kFloat32 &&
+                  denom.scalar_type() == torch::kFloat32,
+              "loss_sum and denom must be fp32");
   launch_ce_fwd_bwd(logits.data_ptr(),
                     reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()),
                     loss_sum.data_ptr<float>(), denom.data_ptr<float>(),
@@ -222,11 +242,25 @@ void adamw(Tensor p, Tensor g, Tensor m, Tensor v, double step, double lr,
     return 0;
   };
   const int gdt = dt_code(g.scalar_type());
+  TORCH_CHECK(g.numel() == n && g.is_contiguous(),
+              "g must be contiguous with p's element count");
+  TORCH_CHECK(m.scalar_type() == torch::kFloat32 && m.numel() == n &&
+                  m.is_contiguous(),
+              "m must be contiguous fp32 with p's element count");
+  TORCH_CHECK(v.scalar_type() == torch::kFloat32 && v.numel() == n &&
+                  v.is_contiguous(),
+              "v must be contiguous fp32 with p's element count");
   int odt = 0;
   if (p_bf16_out.has_value()) {
     odt = dt_code(p_bf16_out->scalar_type());
     TORCH_CHECK(odt != 0, "low-precision publish target must be bf16/fp16");
+    TORCH_CHECK(p_bf16_out->numel() == n && p_bf16_out->is_contiguous(),
+                "publish target must be contiguous with p's element count");
   }
+  if (grad_scale.has_value())
+    TORCH_CHECK(grad_scale->scalar_type() == torch::kFloat32 &&
+                    grad_scale->numel() == 1,
+                "grad_scale must be a single fp32 value");
   const float bc1 = 1.f - powf((float)b1, (float)step);
   const float bc2 = 1.f - powf((float)b2, (float)step);
   launch_adamw(p.data_ptr<float>(), g.data_ptr(), gdt, m.data_ptr<float>(),
@@ -493,12 +527,54 @@ static long long slice_stride(const Tensor& t, const char* nm) {
   return t.stride(0);
 }
 
+// fp32 contiguous (N, Q) per-(chunk, head) rows: dtf / dacs and their grads
+static void check_nq(const Tensor& t, long long N, long long Q,
+                     const char* nm) {
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, nm, " must be fp32");
+  TORCH_CHECK(t.is_contiguous(), nm, " must be contiguous");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == N && t.size(1) == Q, nm,
+              " must have shape (rows/Q*H, Q)");
+}
+
+// contiguous bf16 tensor of exactly `numel` elements
+static void check_bf16_numel(const Tensor& t, long long numel,
+                             const char* nm) {
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, nm, " must be bf16");
+  TORCH_CHECK(t.is_contiguous(), nm, " must be contiguous");
+  TORCH_CHECK(t.numel() == numel, nm, " has the wrong element count");
+}
+
+// per-head fp32 parameter vector (dt_bias, A_log, D)
+static void check_head_vec(const Tensor& t, long long H, const char* nm) {
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.is_contiguous() &&
+                  t.numel() == H,
+              nm, " must be contiguous fp32 with H elements");
+}
+
+// x / z slices of the fused projections: (rows, H*P) with rows % Q == 0
+static long long check_xslice(const Tensor& t, int64_t H, int64_t P,
+                              int64_t Q, const char* nm) {
+  const long long st = slice_stride(t, nm);
+  TORCH_CHECK(H > 0 && P > 0 && P % 8 == 0, "P must be divisible by 8");
+  TORCH_CHECK(Q > 0 && Q % 8 == 0, "Q must be divisible by 8");
+  TORCH_CHECK(t.size(1) == H * P, nm, " must have H*P columns");
+  TORCH_CHECK(t.size(0) % Q == 0, nm, " rows must be a multiple of Q");
+  return st;
+}
+
+static void check_prep_q(long long rows, int64_t Q) {
+  TORCH_CHECK(Q > 0 && Q <= 256 && Q % 64 == 0 && rows % Q == 0,
+              "Q must be 64, 128, 192 or 256 and divide the row count");
+}
+
 std::tuple<Tensor, Tensor> ssd_prep_fwd(Tensor dt, Tensor bias, Tensor alog,
                                         int64_t Q) {
   const long long sdt = slice_stride(dt, "dt");
   const long long rows = dt.size(0);
   const int H = dt.size(1);
-  TORCH_CHECK(rows % Q == 0 && Q <= 256 && Q % 64 == 0);
+  check_prep_q(rows, Q);
+  check_head_vec(bias, H, "bias");
+  check_head_vec(alog, H, "alog");
   const long long N = rows / Q * H;
   auto opt = dt.options().dtype(torch::kFloat32);
   auto dtf = torch::empty({N, Q}, opt);
@@ -516,7 +592,12 @@ std::tuple<Tensor, Tensor, Tensor> ssd_prep_bwd(Tensor ddtf, Tensor ddacs,
   const long long sdt = slice_stride(dt, "dt");
   const long long rows = dt.size(0);
   const int H = dt.size(1);
+  check_prep_q(rows, Q);
+  check_head_vec(bias, H, "bias");
+  check_head_vec(alog, H, "alog");
   const long long N = rows / Q * H;
+  check_nq(ddtf, N, Q, "ddtf");
+  check_nq(ddacs, N, Q, "ddacs");
   auto ddt = torch::empty({rows, (long long)H},
                           dt.options().dtype(torch::kBFloat16));
   auto dbias = torch::zeros({H}, dt.options().dtype(torch::kFloat32));
@@ -531,8 +612,10 @@ std::tuple<Tensor, Tensor, Tensor> ssd_prep_bwd(Tensor ddtf, Tensor ddacs,
 
 std::tuple<Tensor, Tensor> ssd_xdt_fwd(Tensor x, Tensor dtf, Tensor dacs,
                                        int64_t H, int64_t P, int64_t Q) {
-  const long long sx = slice_stride(x, "x");
+  const long long sx = check_xslice(x, H, P, Q, "x");
   const long long rows = x.size(0);
+  check_nq(dtf, rows / Q * H, Q, "dtf");
+  check_nq(dacs, rows / Q * H, Q, "dacs");
   auto xdt = torch::empty({rows, H * P},
                           x.options().dtype(torch::kBFloat16));
   auto xdtd = torch::empty_like(xdt);
@@ -547,8 +630,12 @@ std::tuple<Tensor, Tensor, Tensor> ssd_xdt_bwd(Tensor dxdt, Tensor dxdtd,
                                                Tensor x, Tensor dtf,
                                                Tensor dacs, int64_t H,
                                                int64_t P, int64_t Q) {
-  const long long sx = slice_stride(x, "x");
+  const long long sx = check_xslice(x, H, P, Q, "x");
   const long long rows = x.size(0);
+  check_nq(dtf, rows / Q * H, Q, "dtf");
+  check_nq(dacs, rows / Q * H, Q, "dacs");
+  check_bf16_numel(dxdt, rows * H * P, "dxdt");
+  check_bf16_numel(dxdtd, rows * H * P, "dxdtd");
   auto dx = torch::empty({rows, H * P}, x.options().dtype(torch::kBFloat16));
   auto ddtf = torch::empty_like(dtf);
   auto sdec = torch::empty_like(dacs);
@@ -560,11 +647,27 @@ std::tuple<Tensor, Tensor, Tensor> ssd_xdt_bwd(Tensor dxdt, Tensor dxdtd,
   return {dx, ddtf, sdec};
 }
 
-Tensor ssd_sl_fwd(Tensor dacs, Tensor scores, int64_t H, int64_t G) {
+// dacs (N, Q) fp32 and per-group scores (N/H*G, Q, Q) bf16; returns Q
+static int check_sl(const Tensor& dacs, const Tensor& scores, int64_t H,
+                    int64_t G) {
+  TORCH_CHECK(H > 0 && G > 0 && H % G == 0, "H must be a multiple of G");
+  TORCH_CHECK(dacs.dim() == 2, "dacs must be (N, Q)");
+  const long long N = dacs.size(0), Q = dacs.size(1);
+  TORCH_CHECK(Q > 0 && Q % 8 == 0, "Q must be divisible by 8");
+  TORCH_CHECK(N % H == 0, "dacs rows must be a multiple of H");
+  check_nq(dacs, N, Q, "dacs");
   TORCH_CHECK(scores.scalar_type() == torch::kBFloat16 &&
-              scores.is_contiguous());
+                  scores.is_contiguous(),
+              "scores must be contiguous bf16");
+  TORCH_CHECK(scores.dim() == 3 && scores.size(0) == N / H * G &&
+                  scores.size(1) == Q && scores.size(2) == Q,
+              "scores must have shape (N/H*G, Q, Q)");
+  return (int)Q;
+}
+
+Tensor ssd_sl_fwd(Tensor dacs, Tensor scores, int64_t H, int64_t G) {
+  const int Q = check_sl(dacs, scores, H, G);
   const long long N = dacs.size(0);
-  const int Q = dacs.size(1);
   auto out = torch::empty({N, (long long)Q, (long long)Q},
                           scores.options());
   launch_ssd_sl_fwd(dacs.data_ptr<float>(), scores.data_ptr(),
@@ -575,8 +678,9 @@ Tensor ssd_sl_fwd(Tensor dacs, Tensor scores, int64_t H, int64_t G) {
 
 std::tuple<Tensor, Tensor> ssd_sl_bwd(Tensor g, Tensor scores, Tensor dacs,
                                       int64_t H, int64_t G) {
+  const int Q = check_sl(dacs, scores, H, G);
   const long long N = dacs.size(0);
-  const int Q = dacs.size(1);
+  check_bf16_numel(g, N * Q * Q, "g");
   auto dsh = torch::empty({N, (long long)Q, (long long)Q}, g.options());
   auto dcs = torch::zeros_like(dacs);
   launch_ssd_sl_bwd(g.data_ptr(), scores.data_ptr(), dacs.data_ptr<float>(),
@@ -585,13 +689,24 @@ std::tuple<Tensor, Tensor> ssd_sl_bwd(Tensor g, Tensor scores, Tensor dacs,
   return {dsh, dcs};
 }
 
+static void check_ygate(const Tensor& ydiag, const Tensor& yoff,
+                        const Tensor& dacs, const Tensor& x, const Tensor& Dp,
+                        const Tensor& z, int64_t H, int64_t G, int64_t Q) {
+  TORCH_CHECK(G > 0 && H % G == 0, "H must be a multiple of G");
+  TORCH_CHECK(z.size(0) == x.size(0), "x and z must have the same rows");
+  check_bf16_numel(ydiag, x.numel(), "ydiag");
+  check_bf16_numel(yoff, x.numel(), "yoff");
+  check_nq(dacs, x.size(0) / Q * H, Q, "dacs");
+  check_head_vec(Dp, H, "D");
+}
+
 Tensor ssd_ygate_fwd(Tensor ydiag, Tensor yoff, Tensor dacs, Tensor x,
                      Tensor Dp, Tensor z, int64_t H, int64_t G, int64_t P,
                      int64_t Q) {
-  const long long sx = slice_stride(x, "x");
-  const long long sz = slice_stride(z, "z");
-  TORCH_CHECK(ydiag.is_contiguous() && yoff.is_contiguous());
+  const long long sx = check_xslice(x, H, P, Q, "x");
+  const long long sz = check_xslice(z, H, P, Q, "z");
   const long long rows = x.size(0);
+  check_ygate(ydiag, yoff, dacs, x, Dp, z, H, G, Q);
   auto out = torch::empty({rows, H * P}, x.options().dtype(torch::kBFloat16));
   launch_ssd_ygate_fwd(ydiag.data_ptr(), yoff.data_ptr(),
                        dacs.data_ptr<float>(), x.data_ptr(),
@@ -605,9 +720,11 @@ std::vector<Tensor> ssd_ygate_bwd(Tensor dout, Tensor ydiag, Tensor yoff,
                                   Tensor dacs, Tensor x, Tensor Dp, Tensor z,
                                   int64_t H, int64_t G, int64_t P,
                                   int64_t Q) {
-  const long long sx = slice_stride(x, "x");
-  const long long sz = slice_stride(z, "z");
+  const long long sx = check_xslice(x, H, P, Q, "x");
+  const long long sz = check_xslice(z, H, P, Q, "z");
   const long long rows = x.size(0);
+  check_ygate(ydiag, yoff, dacs, x, Dp, z, H, G, Q);
+  check_bf16_numel(dout, rows * H * P, "dout");
   auto o = x.options().dtype(torch::kBFloat16);
   auto dydiag = torch::empty({rows, H * P}, o);
   auto dyoff = torch::empty({rows, H * P}, o);

@@ -81,6 +81,62 @@ def causal_conv1d(x, weight, bias):
     return F.silu(y).transpose(1, 2).to(x.dtype)
 
 
+# --------------------------------------------------------------------------
+# Oracles of the four fused SSD pieces (ops/hip/ssd.hip), in the layouts
+# and group mapping of Mamba2Mixer._scan_fused. They compute in the dtype
+# they are given (float64 in the tests); backward comes from autograd.
+# Row index of the (N, Q) tensors: n = bc*H + h with bc = b*nc + c.
+# --------------------------------------------------------------------------
+def ssd_prep(dt2d, dt_bias, A_log, Q):
+    """dt2d (b*l, H) -> dtf, dacs (N, Q): dtf = softplus(dt + bias),
+    dacs = chunk-local cumsum of dtf * -exp(A_log)."""
+    rows, H = dt2d.shape
+    dtf = torch.logaddexp(dt2d + dt_bias, torch.zeros_like(dt2d))
+    dtf = dtf.reshape(rows // Q, Q, H).transpose(1, 2)       # (bc, H, Q)
+    dacs = (dtf * -torch.exp(A_log).view(1, H, 1)).cumsum(-1)
+    return dtf.reshape(-1, Q), dacs.reshape(-1, Q)
+
+
+def ssd_xdt(x2d, dtf, dacs, H, P, Q):
+    """x2d (b*l, H*P) -> xdt = x*dtf and xdtd = xdt*exp(dacs_end - dacs),
+    both h-major (bc, H, Q, P) flattened to (b*l, H*P)."""
+    rows = x2d.shape[0]
+    bc = rows // Q
+    xh = x2d.reshape(bc, Q, H, P).permute(0, 2, 1, 3)        # (bc, H, Q, P)
+    cs = dacs.view(bc, H, Q)
+    xdt = xh * dtf.view(bc, H, Q, 1)
+    xdtd = xdt * torch.exp(cs[..., -1:] - cs).unsqueeze(-1)
+    return xdt.reshape(rows, H * P), xdtd.reshape(rows, H * P)
+
+
+def ssd_scores_decay(dacs, scores3d, H, G):
+    """sL[n, i, j] = scores[m, i, j] * exp(dacs[n, i] - dacs[n, j]) for
+    j <= i, else 0; scores per group: m = bc*G + h // (H // G)."""
+    N, Q = dacs.shape
+    rep = H // G
+    diff = dacs[:, :, None] - dacs[:, None, :]
+    mask = torch.tril(torch.ones(Q, Q, dtype=torch.bool, device=dacs.device))
+    L = torch.exp(diff.masked_fill(~mask, -torch.inf))
+    s = scores3d.view(N // H, G, 1, Q, Q).expand(-1, -1, rep, -1, -1)
+    return s.reshape(N, Q, Q) * L
+
+
+def ssd_ygate(ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q):
+    """out = (ydiag + yoff*exp(dacs) + x*D) * silu(z), (b*l, H*P).
+    ydiag h-major (bc, H, Q, P); yoff (bc, G, Q, rep, P)."""
+    rows = x2d.shape[0]
+    bc = rows // Q
+    rep = H // G
+    yd = ydiag.reshape(bc, H, Q, P).permute(0, 2, 1, 3)      # (bc, Q, H, P)
+    yo = yoff.reshape(bc, G, Q, rep, P).permute(0, 2, 1, 3, 4) \
+        .reshape(bc, Q, H, P)
+    sd = torch.exp(dacs.view(bc, H, Q)).permute(0, 2, 1).unsqueeze(-1)
+    xh = x2d.reshape(bc, Q, H, P)
+    zh = z2d.reshape(bc, Q, H, P)
+    y = yd + yo * sd + xh * D.view(1, 1, H, 1)
+    return (y * zh * torch.sigmoid(zh)).reshape(rows, H * P)
+
+
 def adamw_step(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay):
     """In-place fp32 AdamW on flat tensors (the shard update)."""
     p.mul_(1 - lr * weight_decay)

@@ -21,7 +21,7 @@ def naive_ssd(x, dt, A, B, C):
             "bhn,bhp->bhnp", Bh[:, t].double() * dt[:, t, :, None].double(),
             x[:, t].double())
         ys.append(torch.einsum("bhn,bhnp->bhp", Ch[:, t].double(), S))
-    return torch.stack(ys, dim=1).float()
+    return torch.stack(ys, dim=1).to(x.dtype)   # float64 in, float64 out
 
 
 @pytest.mark.parametrize("l,chunk", [(64, 16), (128, 32), (96, 96)])
