@@ -222,6 +222,10 @@ class LlamaBlock(nn.Module):
         self.attn = Attention(cfg)
         self.mlp_norm = RMSNorm(cfg.emb_dim, cfg.norm_eps)
         self.mlp = SwiGLU(cfg)
+        # norm wgrads land in the sharded runtime's flat grad buffer from
+        # the backward kernel itself (ops.rmsnorm; no-op for plain models)
+        self.attn_norm.weight._direct_wgrad = True
+        self.mlp_norm.weight._direct_wgrad = True
 
     def forward(self, x, cos, sin, cache=None, doc_mask=None):
         if cache is None and getattr(self, "_ac_enabled", False) \
@@ -232,10 +236,15 @@ class LlamaBlock(nn.Module):
         return self._forward_impl(x, cos, sin, cache, doc_mask)
 
     def _forward_impl(self, x, cos, sin, cache=None, doc_mask=None):
-        # both residual adds ride the projection GEMM epilogues (addmm)
-        h = self.attn(self.attn_norm(x), cos, sin, cache, residual=x,
-                      doc_mask=doc_mask)
-        return self.mlp(self.mlp_norm(h), residual=h)
+        # both residual adds ride the projection GEMM epilogues (addmm);
+        # the residual stream passes THROUGH each norm op, so in backward
+        # its grad is added inside the norm's dx kernel
+        n, x_res = ops.rmsnorm_residual(x, self.attn_norm.weight,
+                                        self.attn_norm.eps)
+        h = self.attn(n, cos, sin, cache, residual=x_res, doc_mask=doc_mask)
+        n, h_res = ops.rmsnorm_residual(h, self.mlp_norm.weight,
+                                        self.mlp_norm.eps)
+        return self.mlp(n, residual=h_res)
 
     def reset_parameters(self):
         for m in (self.attn_norm, self.attn, self.mlp_norm, self.mlp):
@@ -250,6 +259,7 @@ class Llama(nn.Module):
         self.rot_emb = RotaryEmbedding(cfg.head_dim, cfg.max_expected_seq_len, cfg.rope_theta)
         self.layers = nn.ModuleList([LlamaBlock(cfg) for _ in range(cfg.nlayers)])
         self.norm = RMSNorm(cfg.emb_dim, cfg.norm_eps)
+        self.norm.weight._direct_wgrad = True
         self.lm_head = nn.Linear(cfg.emb_dim, cfg.src_vocab_size, bias=False)
         # token id that ends a document in packed rows; when set, forward()
         # masks attention at document boundaries (config knob `doc_mask`)

@@ -47,31 +47,159 @@ def _require_ext(op):
 # --------------------------------------------------------------------------
 # RMSNorm
 # --------------------------------------------------------------------------
+# Norm weights follow the direct-wgrad protocol of linear_flat (below):
+# a weight the sharded runtime attached to its flat grad buffer
+# (`_flat_grad_view`, `_wgrad_done`, `_wgrad_fresh`) gets its grad written
+# into that view by the backward kernel itself (bf16, overwrite on the
+# first touch since zero_grad, accumulate after) and autograd sees None.
+# Per norm and step that removes the fp32 zero-fill, the cast, autograd's
+# accumulate and the zero-fill of the slice in zero_grad.
+def _direct_wgrad_on(weight):
+    return (getattr(weight, "_flat_grad_view", None) is not None
+            and weight.requires_grad and torch.is_grad_enabled())
+
+
+def _stash_wgrad_target(ctx, weight):
+    # attribute holders stashed at forward time: saved_tensors can return
+    # attr-less re-wrapped tensors (e.g. under AC recompute)
+    ctx.gview = weight._flat_grad_view
+    ctx.wobj = weight
+    ctx.cb = getattr(weight, "_wgrad_done", None)
+
+
+def _take_wgrad_fresh(ctx):
+    """True if this is the first write since zero_grad; clears the flag."""
+    fresh = getattr(ctx.wobj, "_wgrad_fresh", False)
+    ctx.wobj._wgrad_fresh = False
+    return fresh
+
+
+class _WgradSinkFn(torch.autograd.Function):
+    """Identity on a direct-wgrad weight whose backward lands the incoming
+    grad in the flat grad view. Puts the paths that never reach a
+    grad-writing kernel (CPU reference, fp32 activations, the fp16
+    bridge) under the same protocol."""
+
+    @staticmethod
+    def forward(ctx, weight):
+        _stash_wgrad_target(ctx, weight)
+        return weight.view_as(weight)
+
+    @staticmethod
+    def backward(ctx, dw):
+        if _take_wgrad_fresh(ctx):
+            ctx.gview.copy_(dw)
+        else:
+            ctx.gview.add_(dw)
+        if ctx.cb is not None:
+            ctx.cb()
+        return None
+
+
+def _rmsnorm_backward(ctx, dy, dextra):
+    x2d, weight, rinv = ctx.saved_tensors
+    if dy is None:
+        dy = torch.zeros_like(x2d)
+    dy = dy.contiguous().view_as(x2d)
+    if dextra is not None:
+        dextra = dextra.contiguous().view_as(x2d)
+    if ctx.direct:
+        dx = _C.rmsnorm_bwd_into(dy, x2d, weight, rinv, dextra,
+                                 ctx.gview.view(-1),
+                                 not _take_wgrad_fresh(ctx))
+        if ctx.cb is not None:
+            ctx.cb()
+        return dx.view(ctx.shape), None
+    dx, dw = _C.rmsnorm_bwd(dy, x2d, weight, rinv, dextra)
+    return dx.view(ctx.shape), dw.to(weight.dtype)
+
+
 class _RMSNormFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, eps):
+    def forward(ctx, x, weight, eps, direct=False):
         ext = _require_ext("rmsnorm")
         x2d = x.contiguous().view(-1, x.shape[-1])
         y, rinv = ext.rmsnorm_fwd(x2d, weight, eps)
         ctx.save_for_backward(x2d, weight, rinv)
         ctx.shape = x.shape
+        ctx.direct = direct
+        if direct:
+            _stash_wgrad_target(ctx, weight)
         return y.view(x.shape)
 
     @staticmethod
     def backward(ctx, dy):
-        x2d, weight, rinv = ctx.saved_tensors
-        dx, dw = _C.rmsnorm_bwd(dy.contiguous().view_as(x2d), x2d, weight,
-                                rinv, None)
-        return dx.view(ctx.shape), dw.to(weight.dtype), None
+        dx, dw = _rmsnorm_backward(ctx, dy, None)
+        return dx, dw, None, None
+
+
+class _RMSNormResidualFn(torch.autograd.Function):
+    """(rmsnorm(x), x): the second output carries the residual stream past
+    the norm, so its grad arrives here and rides the dx kernel's `dextra`
+    operand instead of a separate elementwise add."""
+
+    @staticmethod
+    def forward(ctx, x, weight, eps, direct=False):
+        ext = _require_ext("rmsnorm")
+        x2d = x.contiguous().view(-1, x.shape[-1])
+        y, rinv = ext.rmsnorm_fwd(x2d, weight, eps)
+        ctx.save_for_backward(x2d, weight, rinv)
+        ctx.shape = x.shape
+        ctx.direct = direct
+        if direct:
+            _stash_wgrad_target(ctx, weight)
+        ctx.set_materialize_grads(False)
+        # x_res is a view of an input made inside a custom Function:
+        # autograd raises if a caller later modifies it in place (a
+        # `residual.add_` epilogue would). Treat it as read-only.
+        return y.view(x.shape), x2d.view(x.shape)
+
+    @staticmethod
+    def backward(ctx, dy, dres):
+        dx, dw = _rmsnorm_backward(ctx, dy, dres)
+        return dx, dw, None, None
+
+
+def _rmsnorm_dispatch(fn, x, weight, eps):
+    """GPU kernel path of rmsnorm / rmsnorm_residual; None where the
+    reference implementation applies (CPU, fp32 activations)."""
+    if not (x.is_cuda and x.dtype != torch.float32):
+        return None
+    if x.dtype == torch.float16:
+        if _direct_wgrad_on(weight):
+            weight = _WgradSinkFn.apply(weight)
+        # only the norm goes through the bf16 bridge: the residual
+        # stream stays the caller's exact fp16 x, and autograd adds its
+        # grad in fp16
+        y = _RMSNormFn.apply(x.bfloat16(), weight.bfloat16(), eps).half()
+        return y if fn is _RMSNormFn else (y, x)
+    direct = _direct_wgrad_on(weight) and weight.dtype == torch.bfloat16
+    if not direct and _direct_wgrad_on(weight):
+        weight = _WgradSinkFn.apply(weight)
+    return fn.apply(x, weight, eps, direct)
 
 
 def rmsnorm(x, weight, eps=1e-6):
-    if x.is_cuda and x.dtype != torch.float32:
-        if x.dtype == torch.float16:
-            return _RMSNormFn.apply(x.bfloat16(), weight.bfloat16(),
-                                    eps).half()
-        return _RMSNormFn.apply(x, weight, eps)
+    y = _rmsnorm_dispatch(_RMSNormFn, x, weight, eps)
+    if y is not None:
+        return y
+    if _direct_wgrad_on(weight):
+        weight = _WgradSinkFn.apply(weight)
     return reference.rmsnorm(x, weight, eps)
+
+
+def rmsnorm_residual(x, weight, eps=1e-6):
+    """(rmsnorm(x), x_res) with x_res the values of x: feed x_res as the
+    residual of the projection that follows the norm, and the backward
+    adds the residual-stream grad inside the norm's dx kernel. fp16, fp32
+    and CPU inputs get x itself back and the add stays autograd's. Do not
+    modify x_res in place."""
+    out = _rmsnorm_dispatch(_RMSNormResidualFn, x, weight, eps)
+    if out is not None:
+        return out
+    if _direct_wgrad_on(weight):
+        weight = _WgradSinkFn.apply(weight)
+    return reference.rmsnorm(x, weight, eps), x
 
 
 class _AddRMSNormFn(torch.autograd.Function):

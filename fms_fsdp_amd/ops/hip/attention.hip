@@ -477,22 +477,26 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(
 // ---------------------------------------------------------------------
 // Backward preprocess: delta[b,h,s] = rowsum(dO * O) fp32
 // ---------------------------------------------------------------------
-__global__ void attn_bwd_delta_kernel(const short* __restrict__ dog,
-                                      const short* __restrict__ og,
-                                      float* __restrict__ delta,
-                                      int D, int S, int H, long long rows) {
-  // one wave per row; input rows are (b, s, h) order, delta is (b, h, s)
-  const long long row = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / 64;
-  if (row >= rows) return;
-  const int lane = threadIdx.x & 63;
-  const short* dop = dog + row * D;
-  const short* op = og + row * D;
+// LPR = D/8 lanes per row, 64/LPR rows per wave: every lane loads 16 bytes
+// of dO and of O, and consecutive lanes read consecutive memory (the rows
+// are contiguous). Sub-wave xor reduction over the row's LPR lanes.
+template <int LPR>
+__global__ __launch_bounds__(256) void attn_bwd_delta_kernel(
+    const bf16x8* __restrict__ dog, const bf16x8* __restrict__ og,
+    float* __restrict__ delta, int S, int H, long long rows) {
+  // input rows are (b, s, h) order, delta is (b, h, s)
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long row = gid / LPR;
   float acc = 0.f;
-  for (int i = lane * 2; i < D; i += 128) {
-    acc += bf2f(dop[i]) * bf2f(op[i]) + bf2f(dop[i + 1]) * bf2f(op[i + 1]);
+  if (row < rows) {   // a row's lanes agree; idle lanes still shuffle
+    const bf16x8 a = dog[gid], c = og[gid];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc += bf2f(a.v[j]) * bf2f(c.v[j]);
   }
-  acc = wave_reduce_sum(acc);
-  if (lane == 0) {
+#pragma unroll
+  for (int off = LPR / 2; off > 0; off >>= 1)
+    acc += __shfl_xor(acc, off, LPR);
+  if (row < rows && (threadIdx.x & (LPR - 1)) == 0) {
     const long long b = row / ((long long)S * H);
     const int si = (int)((row / H) % S);
     const int hi = (int)(row % H);
@@ -1648,6 +1652,19 @@ void launch_attn_fwd(const void* q, const void* k, const void* v, void* o,
         S, H, KVH, scale, vstride, sched);
 }
 
+// delta[b,h,s] = rowsum(dO * O); do_ and o contiguous (b,s,h,d), d 64 or 128
+void launch_attn_bwd_delta(const void* do_, const void* o, float* delta,
+                           int B, int S, int H, int D, hipStream_t stream) {
+  const long long rows = (long long)B * S * H;
+  const unsigned grid = (unsigned)((rows * (D / 8) + 255) / 256);
+  if (D == 128)
+    attn_bwd_delta_kernel<16><<<grid, 256, 0, stream>>>(
+        (const bf16x8*)do_, (const bf16x8*)o, delta, S, H, rows);
+  else
+    attn_bwd_delta_kernel<8><<<grid, 256, 0, stream>>>(
+        (const bf16x8*)do_, (const bf16x8*)o, delta, S, H, rows);
+}
+
 void launch_attn_bwd(const void* do_, const void* q, const void* k,
                      const void* v, const void* o, const float* lse, void* dq,
                      void* dk, void* dv, float* delta_ws, void* ds_ws,
@@ -1655,9 +1672,7 @@ void launch_attn_bwd(const void* do_, const void* q, const void* k,
                      int KVH, int D, float scale, int out_bf16,
                      long long vstride, long long dvstride,
                      hipStream_t stream) {
-  const long long rows = (long long)B * S * H;
-  attn_bwd_delta_kernel<<<(int)((rows * 64 + 255) / 256), 256, 0, stream>>>(
-      (const short*)do_, (const short*)o, delta_ws, D, S, H, rows);
+  launch_attn_bwd_delta(do_, o, delta_ws, B, S, H, D, stream);
   if (D == 128)
     attn_bwd_launch<128>(do_, q, k, v, lse, dq, dk, dv, delta_ws, ds_ws, B, S,
                          H, KVH, scale, out_bf16, vstride, dvstride, stream);
@@ -1691,9 +1706,7 @@ void launch_attn_bwd_doc(const void* do_, const void* q, const void* k,
                          int S, int H, int KVH, int D, float scale,
                          int out_bf16, long long vstride, long long dvstride,
                          hipStream_t stream) {
-  const long long rows = (long long)B * S * H;
-  attn_bwd_delta_kernel<<<(int)((rows * 64 + 255) / 256), 256, 0, stream>>>(
-      (const short*)do_, (const short*)o, delta_ws, D, S, H, rows);
+  launch_attn_bwd_delta(do_, o, delta_ws, B, S, H, D, stream);
   if (D == 128)
     attn_bwd_doc_launch<128>(do_, q, k, v, lse, dq, dk, dv, delta_ws,
                              doc_start, doc_end, B, S, H, KVH, scale,

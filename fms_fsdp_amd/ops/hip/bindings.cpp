@@ -19,6 +19,12 @@ void launch_rmsnorm_bwd(const void*, const void*, const void*, const float*,
                         const void*, void*, float*, int, int, hipStream_t);
 void launch_add_rmsnorm_fwd(const void*, const void*, const void*, void*,
                             void*, float*, int, int, float, hipStream_t);
+int rmsnorm_bwd_grid(int);
+int rmsnorm_bwd_nparts(int, int);
+void launch_rmsnorm_bwd_fused(const void*, const void*, const void*,
+                              const float*, const void*, void*, float*, int,
+                              float*, void*, int, int, int, hipStream_t);
+void launch_rmsnorm_dw_store(const float*, void*, int, int, hipStream_t);
 void launch_rope(const void*, void*, const float*, const float*, int, int,
                  int, int, int, long long, long long, hipStream_t);
 void launch_swiglu_fwd(const void*, void*, long long, int, hipStream_t);
@@ -43,6 +49,8 @@ void launch_attn_bwd_doc(const void*, const void*, const void*, const void*,
                          const void*, const float*, void*, void*, void*,
                          float*, const int*, const int*, int, int, int, int,
                          int, float, int, long long, long long, hipStream_t);
+void launch_attn_bwd_delta(const void*, const void*, float*, int, int, int,
+                           int, hipStream_t);
 int attn_sched_mode(int);
 int attn_dkv_mode(int);
 long long attn_bwd_ws_limit(long long);
@@ -102,9 +110,9 @@ std::tuple<Tensor, Tensor> rmsnorm_fwd(Tensor x, Tensor w, double eps) {
   return {y, rinv};
 }
 
-std::tuple<Tensor, Tensor> rmsnorm_bwd(Tensor dy, Tensor x, Tensor w,
-                                       Tensor rinv,
-                                       c10::optional<Tensor> dextra) {
+static void check_rmsnorm_bwd_args(const Tensor& dy, const Tensor& x,
+                                   const Tensor& w, const Tensor& rinv,
+                                   const c10::optional<Tensor>& dextra) {
   CHECK_BF16_CONTIG(dy);
   CHECK_BF16_CONTIG(x);
   CHECK_BF16_CONTIG(w);
@@ -121,14 +129,79 @@ std::tuple<Tensor, Tensor> rmsnorm_bwd(Tensor dy, Tensor x, Tensor w,
                     dextra->is_contiguous() && dextra->sizes() == x.sizes(),
                 "dextra must have x's shape and dtype");
   }
+}
+
+// dx and dw in one pass over dy and x (rmsnorm.hip): per-block fp32
+// partials, summed in a fixed order, so dw is deterministic and needs no
+// zero-fill. H > 8192 keeps the two-kernel path with fp32 atomics.
+std::tuple<Tensor, Tensor> rmsnorm_bwd(Tensor dy, Tensor x, Tensor w,
+                                       Tensor rinv,
+                                       c10::optional<Tensor> dextra) {
+  check_rmsnorm_bwd_args(dy, x, w, rinv, dextra);
+  const int rows = x.size(0), H = x.size(1);
+  const void* de = dextra.has_value() ? dextra->data_ptr() : nullptr;
+  auto f32 = x.options().dtype(torch::kFloat32);
   auto dx = torch::empty_like(x);
-  auto dw = torch::zeros({H}, x.options().dtype(torch::kFloat32));
-  launch_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
-                     rinv.data_ptr<float>(),
-                     dextra.has_value() ? dextra->data_ptr() : nullptr,
-                     dx.data_ptr(), dw.data_ptr<float>(), rows, H,
-                     cur_stream());
+  const int nparts = rmsnorm_bwd_nparts(rows, H);
+  if (nparts == 0) {
+    auto dw = torch::zeros({H}, f32);
+    launch_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
+                       rinv.data_ptr<float>(), de, dx.data_ptr(),
+                       dw.data_ptr<float>(), rows, H, cur_stream());
+    return {dx, dw};
+  }
+  auto dw = torch::empty({H}, f32);
+  auto part = torch::empty({nparts, H}, f32);
+  launch_rmsnorm_bwd_fused(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
+                           rinv.data_ptr<float>(), de, dx.data_ptr(),
+                           part.data_ptr<float>(), nparts,
+                           dw.data_ptr<float>(), nullptr, 0, rows, H,
+                           cur_stream());
   return {dx, dw};
+}
+
+// rmsnorm_bwd with dw rounded to bf16 straight into dw_dst (a slice of
+// the sharded runtime's flat grad buffer): accumulate=false overwrites,
+// accumulate=true adds to what is there with one rounding. Returns dx.
+Tensor rmsnorm_bwd_into(Tensor dy, Tensor x, Tensor w, Tensor rinv,
+                        c10::optional<Tensor> dextra, Tensor dw_dst,
+                        bool accumulate) {
+  check_rmsnorm_bwd_args(dy, x, w, rinv, dextra);
+  const int rows = x.size(0), H = x.size(1);
+  TORCH_CHECK(dw_dst.scalar_type() == torch::kBFloat16 &&
+                  dw_dst.is_contiguous() && dw_dst.numel() == H &&
+                  dw_dst.device() == x.device(),
+              "dw_dst must be contiguous bf16 with H elements on x's device");
+  const void* de = dextra.has_value() ? dextra->data_ptr() : nullptr;
+  auto f32 = x.options().dtype(torch::kFloat32);
+  auto dx = torch::empty_like(x);
+  const int mode = accumulate ? 2 : 1;
+  const int nparts = rmsnorm_bwd_nparts(rows, H);
+  if (nparts == 0) {
+    auto dw = torch::zeros({H}, f32);
+    launch_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
+                       rinv.data_ptr<float>(), de, dx.data_ptr(),
+                       dw.data_ptr<float>(), rows, H, cur_stream());
+    launch_rmsnorm_dw_store(dw.data_ptr<float>(), dw_dst.data_ptr(), mode, H,
+                            cur_stream());
+    return dx;
+  }
+  auto part = torch::empty({nparts, H}, f32);
+  launch_rmsnorm_bwd_fused(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
+                           rinv.data_ptr<float>(), de, dx.data_ptr(),
+                           part.data_ptr<float>(), nparts, nullptr,
+                           dw_dst.data_ptr(), mode, rows, H, cur_stream());
+  return dx;
+}
+
+// Get/set the block count cap of the fused RMSNorm backward (None =
+// query). Returns the value in force before the call. Tuning and test
+// knob only: the value is an unsynchronised process-global.
+int64_t rmsnorm_bwd_grid_py(c10::optional<int64_t> grid) {
+  if (grid.has_value())
+    TORCH_CHECK(*grid >= 1 && *grid <= 65536,
+                "rmsnorm_bwd_grid: expected 1..65536, got ", *grid);
+  return rmsnorm_bwd_grid(grid.has_value() ? (int)*grid : -1);
 }
 
 std::tuple<Tensor, Tensor, Tensor> add_rmsnorm_fwd(Tensor x, Tensor res,
@@ -381,6 +454,21 @@ std::tuple<Tensor, Tensor, Tensor> attn_bwd(Tensor do_, Tensor q, Tensor k,
                   h, kvh, d, scale, out_bf16 ? 1 : 0, vs, dvs, cur_stream());
   if (out_bf16) return {dq, dk, dv};
   return {dq, dk.to(torch::kBFloat16), dv.to(torch::kBFloat16)};
+}
+
+// The backward's preprocess on its own: delta (b, h, s) fp32 =
+// rowsum(dO * O) over head_dim, dO and O contiguous (b, s, h, d) bf16.
+Tensor attn_bwd_delta(Tensor do_, Tensor o) {
+  CHECK_BF16_CONTIG(do_);
+  CHECK_BF16_CONTIG(o);
+  TORCH_CHECK(do_.dim() == 4 && do_.sizes() == o.sizes(),
+              "do and o must be (b, s, h, d) of one shape");
+  const int b = o.size(0), s = o.size(1), h = o.size(2), d = o.size(3);
+  TORCH_CHECK(d == 64 || d == 128, "head_dim must be 64 or 128");
+  auto delta = torch::empty({b, h, s}, o.options().dtype(torch::kFloat32));
+  launch_attn_bwd_delta(do_.data_ptr(), o.data_ptr(), delta.data_ptr<float>(),
+                        b, s, h, d, cur_stream());
+  return delta;
 }
 
 // (b, s) int32 document boundaries of the masked attention kernels
@@ -749,6 +837,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("cconv_bwd", &cconv_bwd);
   mod.def("rmsnorm_fwd", &rmsnorm_fwd);
   mod.def("rmsnorm_bwd", &rmsnorm_bwd);
+  mod.def("rmsnorm_bwd_into", &rmsnorm_bwd_into);
+  mod.def("rmsnorm_bwd_grid", &rmsnorm_bwd_grid_py,
+          pybind11::arg("grid") = pybind11::none());
   mod.def("add_rmsnorm_fwd", &add_rmsnorm_fwd);
   mod.def("rope_fwd", &rope_fwd);
   mod.def("rope_into", &rope_into);
@@ -768,6 +859,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ssd_ygate_bwd", &ssd_ygate_bwd);
   mod.def("attn_fwd", &attn_fwd);
   mod.def("attn_bwd", &attn_bwd);
+  mod.def("attn_bwd_delta", &attn_bwd_delta);
   mod.def("attn_fwd_doc", &attn_fwd_doc);
   mod.def("attn_bwd_doc", &attn_bwd_doc);
   mod.def("attn_sched_mode", &attn_sched_mode_py,
