@@ -291,7 +291,44 @@ def rope_apply(q, k, cos, sin):
 # opt weights in by setting `weight._direct_wgrad = True`. Saves one
 # full read+write pass over every projection grad per step (the
 # CUDAFunctor_add kernels: ~8.5 ms/step on Llama2-7B, profiles/).
+#
+# The wgrad dW = dy^T @ x finds both operands strided along the tokens
+# (BLAS "NT"), hipBLASLt's slowest class on MI355X. _C.wgrad_tn first
+# transposes dy and x with transpose.hip into transient token-contiguous
+# copies, and the same product then runs in the forward's class ("TN").
+# It pays where the GEMM saves more than the two copy-speed transposes
+# cost. Measured (profiles/7b_1gpu_step_wgrad_tn.md): at 8192 tokens the
+# 7B block's qkv, gate|up and down projections gain 54-188 us each and
+# the square 4096 x 4096 one loses 18 us; at 4096 tokens and below, on
+# hipBLASLt's default algorithms, wins and losses are mixed. Hence:
+# tokens >= 8192 and a weight of at least 4096 x 8192 elements.
+# FMS_AMD_WGRAD=nt keeps every wgrad on the old route.
 # --------------------------------------------------------------------------
+_WGRAD_TN_MIN_TOKENS = 8192
+_WGRAD_TN_MIN_WEIGHT = 4096 * 8192   # out * in
+
+
+def _wgrad_mode(dy2, x2):
+    """_C.wgrad_tn mode for this wgrad; 0 = plain addmm on the operands
+    as they are."""
+    if _C is None or os.environ.get("FMS_AMD_WGRAD") == "nt":
+        return 0
+    if not (dy2.is_cuda and x2.is_cuda and dy2.dtype == torch.bfloat16
+            and x2.dtype == torch.bfloat16):
+        return 0
+    tokens, out = dy2.shape
+    inn = x2.shape[1]
+    if tokens % 8 or out % 8 or inn % 8:
+        return 0
+    if tokens < _WGRAD_TN_MIN_TOKENS or out * inn < _WGRAD_TN_MIN_WEIGHT:
+        return 0
+    for t in (dy2, x2):     # what transpose.hip reads without a copy
+        if (t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < t.shape[1]
+                or t.data_ptr() % 16):
+            return 0
+    return 3
+
+
 class _DirectWgradLinearFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, residual):
@@ -316,19 +353,24 @@ class _DirectWgradLinearFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1])
         x2 = x.reshape(-1, x.shape[-1])
         # NOTE: rerouting this dgrad through a transposed weight copy
-        # (mm(dy, wT.t()) = hipBLASLt's faster "NN" class instead of the
-        # "NT" class this layout hits) measured 29 ms/step SLOWER on the
+        # (mm(dy, wT.t()) = hipBLASLt's faster "TN" class instead of the
+        # "NN" class this layout hits) measured 29 ms/step SLOWER on the
         # 7B bench — the .t().contiguous() sweeps cost more than the
         # GEMM class difference saves. Measured and rejected.
         dx = (dy2 @ w).view(x.shape)
         # wgrad straight into the flat grad buffer. First touch since
         # zero_grad overwrites (beta=0) so the runtime never has to
         # zero-fill these slices; later touches accumulate (beta=1).
-        if getattr(ctx.wobj, "_wgrad_fresh", False):
+        fresh = getattr(ctx.wobj, "_wgrad_fresh", False)
+        mode = _wgrad_mode(dy2, x2)
+        if mode:
+            _C.wgrad_tn(dy2, x2, ctx.gview, not fresh, mode)
+        elif fresh:
             torch.addmm(ctx.gview, dy2.t(), x2, beta=0, out=ctx.gview)
-            ctx.wobj._wgrad_fresh = False
         else:
             ctx.gview.addmm_(dy2.t(), x2)
+        if fresh:
+            ctx.wobj._wgrad_fresh = False
         if ctx.cb is not None:
             ctx.cb()
         dres = dy.reshape(ctx.res_shape) if ctx.res_shape is not None else None

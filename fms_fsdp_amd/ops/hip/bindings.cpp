@@ -30,6 +30,8 @@ void launch_rope(const void*, void*, const float*, const float*, int, int,
 void launch_swiglu_fwd(const void*, void*, long long, int, hipStream_t);
 void launch_swiglu_bwd(const void*, const void*, void*, long long, int,
                        hipStream_t);
+void launch_transpose_bf16(const void*, void*, long long, long long,
+                           long long, hipStream_t);
 void launch_ce_fwd_bwd(void*, const long long*, float*, const float*,
                        long long, int, int, hipStream_t);
 void launch_adamw(float*, const void*, int, float*, float*, void*, int,
@@ -282,6 +284,70 @@ Tensor swiglu_bwd(Tensor dy, Tensor gu) {
                     H2 / 2, cur_stream());
   return dgu;
 }
+
+// src (rows, cols) bf16 with unit column stride and a row stride >= cols
+// (a column slice of a wider buffer qualifies) -> contiguous (cols, rows).
+static bool transpose_src_ok(const Tensor& t) {
+  return t.is_cuda() && t.scalar_type() == torch::kBFloat16 && t.dim() == 2 &&
+         t.size(1) % 8 == 0 && t.size(0) > 0 && t.size(1) > 0 &&
+         t.stride(1) == 1 && t.stride(0) >= t.size(1) &&
+         t.stride(0) % 8 == 0 &&
+         reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// `out`, if given, is the contiguous (cols, rows) destination.
+Tensor transpose_bf16(Tensor src, c10::optional<Tensor> out) {
+  TORCH_CHECK(transpose_src_ok(src),
+              "transpose_bf16: src must be a 2-D bf16 GPU tensor, cols % 8 == "
+              "0, unit column stride, row stride a multiple of 8 and >= "
+              "cols, 16-byte aligned");
+  const long long rows = src.size(0), cols = src.size(1);
+  TORCH_CHECK((rows + 63) / 64 * ((cols + 63) / 64) < (1LL << 31),
+              "transpose_bf16: too many tiles for one grid");
+  Tensor dst;
+  if (out.has_value()) {
+    dst = *out;
+    TORCH_CHECK(dst.is_cuda() && dst.scalar_type() == torch::kBFloat16 &&
+                    dst.dim() == 2 && dst.size(0) == cols &&
+                    dst.size(1) == rows && dst.is_contiguous() &&
+                    reinterpret_cast<uintptr_t>(dst.data_ptr()) % 16 == 0,
+                "transpose_bf16: out must be a contiguous, 16-byte aligned "
+                "bf16 GPU tensor of shape (cols, rows)");
+  } else {
+    dst = torch::empty({cols, rows}, src.options());
+  }
+  launch_transpose_bf16(src.data_ptr(), dst.data_ptr(), rows, cols,
+                        src.stride(0), cur_stream());
+  return dst;
+}
+
+// dW = dy2^T @ x2 into gview (out, in) with the operands that `mode` names
+// transposed first, so that the GEMM finds them contiguous along the
+// tokens: bit 0 = dy2 (tokens, out), bit 1 = x2 (tokens, in). Mode 3 is
+// the forward's GEMM class (BLAS "TN"), 1 is "NN", 2 is "TT"; the
+// untransposed call is the "NT" class. The transposed copies come from
+// the caching allocator and die with this call (stream-ordered reuse).
+// accumulate=false overwrites: beta is 0 and gview's old contents are
+// never read.
+static int64_t wgrad_tn_count = 0;
+
+void wgrad_tn(Tensor dy2, Tensor x2, Tensor gview, bool accumulate,
+              int64_t mode) {
+  TORCH_CHECK(mode >= 1 && mode <= 3, "wgrad_tn: mode must be 1, 2 or 3");
+  TORCH_CHECK(dy2.dim() == 2 && x2.dim() == 2 && dy2.size(0) == x2.size(0),
+              "wgrad_tn: dy2 (tokens, out) and x2 (tokens, in) expected");
+  TORCH_CHECK(gview.scalar_type() == torch::kBFloat16 && gview.dim() == 2 &&
+                  gview.size(0) == dy2.size(1) && gview.size(1) == x2.size(1),
+              "wgrad_tn: gview must be bf16 (out, in)");
+  TORCH_CHECK(dy2.size(0) % 8 == 0, "wgrad_tn: tokens % 8 != 0");
+  Tensor a = (mode & 1) ? transpose_bf16(dy2, c10::nullopt) : dy2.t();
+  Tensor b = (mode & 2) ? transpose_bf16(x2, c10::nullopt).t() : x2;
+  at::addmm_out(gview, gview, a, b, accumulate ? 1 : 0, 1);
+  ++wgrad_tn_count;
+}
+
+// Calls of wgrad_tn so far: lets a test see which route a backward took.
+int64_t wgrad_tn_calls() { return wgrad_tn_count; }
 
 void ce_fwd_bwd(Tensor logits, Tensor labels, Tensor loss_sum, Tensor denom,
                 int64_t ignore_index) {
@@ -845,6 +911,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("rope_into", &rope_into);
   mod.def("swiglu_fwd", &swiglu_fwd);
   mod.def("swiglu_bwd", &swiglu_bwd);
+  mod.def("transpose_bf16", &transpose_bf16, pybind11::arg("src"),
+          pybind11::arg("out") = pybind11::none());
+  mod.def("wgrad_tn", &wgrad_tn);
+  mod.def("wgrad_tn_calls", &wgrad_tn_calls);
   mod.def("ce_fwd_bwd", &ce_fwd_bwd);
   mod.def("adamw", &adamw);
   mod.def("sq_norm_accum", &sq_norm_accum);

@@ -21,7 +21,7 @@ BUILD_DIR = os.path.join(REPO, "build", "hip_objs")
 
 HIP_SOURCES = ["rmsnorm.hip", "rope.hip", "swiglu.hip", "cross_entropy.hip",
                "adamw.hip", "attention.hip", "causal_conv1d.hip", "ssd.hip",
-               "gemm_nt.hip"]
+               "gemm_nt.hip", "transpose.hip"]
 # headers the .hip sources include: a newer header rebuilds every object
 HIP_HEADERS = ["common.h", "attn_sched.h", "attn_ws.h"]
 
