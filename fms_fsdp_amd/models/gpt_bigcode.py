@@ -36,6 +36,7 @@ class BigCodeAttention(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         self.nheads = cfg.nheads
+        self.kvheads = 1
         self.head_dim = cfg.head_dim
         # multi-query: one shared kv head
         self.qkv = nn.Linear(cfg.emb_dim, (cfg.nheads + 2) * cfg.head_dim)
@@ -53,7 +54,11 @@ class BigCodeAttention(nn.Module):
         q = q.view(b, s, self.nheads, self.head_dim)
         k = k.view(b, s, 1, self.head_dim)
         v = v.view(b, s, 1, self.head_dim)
-        if cache is not None:
+        if isinstance(cache, ops.KVCache):
+            # preallocated cache (generate()): append without a rotation,
+            # then the decode kernel over the cache
+            o = ops.attention_cached(q, k, v, cache)
+        elif cache is not None:
             if cache.get("k") is not None:
                 k = torch.cat([cache["k"], k], dim=1)
                 v = torch.cat([cache["v"], v], dim=1)
@@ -127,7 +132,11 @@ class GPTBigCode(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens, temperature=1.0,
                  do_sample=True, include_embeds=False):
-        caches = [{} for _ in self.layers]
+        b, s0 = input_ids.shape
+        w = self.embedding.weight
+        caches = [ops.KVCache(b, s0 + max_new_tokens, layer.attn.kvheads,
+                              layer.attn.head_dim, w.dtype, w.device)
+                  for layer in self.layers]
         tokens = input_ids
         embeds = []
         cur = input_ids

@@ -166,10 +166,16 @@ class Attention(nn.Module):
         q = q.view(b, s, self.nheads, self.head_dim)
         k = k.view(b, s, self.kvheads, self.head_dim)
         v = v.view(b, s, self.kvheads, self.head_dim)
+        if isinstance(cache, ops.KVCache):
+            # preallocated cache (generate()): q/k/v stay slices of the
+            # fused projection; RoPE and the append are one kernel, the
+            # attention a decode kernel over the cache (ops.attention_cached)
+            o = ops.attention_cached(q, k, v, cache, cos, sin)
+            return self._project_out(o.reshape(b, s, -1), residual, b, s)
         q, k = ops.rope_apply(q, k, cos, sin)
         if cache is not None:
-            # decode path with KV cache (speculator stage-2 generation);
-            # memory-bound small-batch attention runs through torch SDPA.
+            # plain dict cache: the former route, K/V grown by torch.cat
+            # and torch SDPA (generate() passes an ops.KVCache instead)
             import torch.nn.functional as F
             if cache.get("k") is not None:
                 k = torch.cat([cache["k"], k], dim=1)
@@ -296,13 +302,20 @@ class Llama(nn.Module):
         hidden state of each generated position (reference analog:
         speculator/train_speculator_utils.py:28-118 generate())."""
         b, s0 = input_ids.shape
-        caches = [{} for _ in self.layers]
+        caches = None
         tokens = input_ids
         embeds = []
         cur = input_ids
         pos = 0
         for step in range(max_new_tokens):
             x = self.embedding(cur)
+            if caches is None:
+                # one preallocated cache per layer; head counts from the
+                # module (tensor parallelism has already divided them)
+                caches = [ops.KVCache(b, s0 + max_new_tokens,
+                                      layer.attn.kvheads, layer.attn.head_dim,
+                                      x.dtype, x.device)
+                          for layer in self.layers]
             total = pos + cur.shape[1]
             cos, sin = self.rot_emb.get(total, x.device)
             cos_c, sin_c = cos[pos:total], sin[pos:total]

@@ -136,13 +136,19 @@ class Mixtral(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids, max_new_tokens, temperature=1.0,
                  do_sample=True, include_embeds=False):
-        caches = [{} for _ in self.layers]
+        b, s0 = input_ids.shape
+        caches = None
         tokens = input_ids
         embeds = []
         cur = input_ids
         pos = 0
         for _ in range(max_new_tokens):
             x = self.embedding(cur)
+            if caches is None:      # one preallocated cache per layer
+                caches = [ops.KVCache(b, s0 + max_new_tokens,
+                                      layer.attn.kvheads, layer.attn.head_dim,
+                                      x.dtype, x.device)
+                          for layer in self.layers]
             total = pos + cur.shape[1]
             cos, sin = self.rot_emb.get(total, x.device)
             cos_c, sin_c = cos[pos:total], sin[pos:total]

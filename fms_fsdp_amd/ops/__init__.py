@@ -594,6 +594,158 @@ def attention_causal(q, k, v, doc_mask=None):
     return reference.attention_causal(q, k, v, doc_mask)
 
 
+# --------------------------------------------------------------------------
+# KV-cache decode: preallocated in-place cache, fused append, split-KV
+# attention for one query position (attn_decode.hip)
+# --------------------------------------------------------------------------
+class KVCache:
+    """Preallocated K/V history of one attention layer: `k` and `v` of
+    shape (b, capacity, kvheads, head_dim) and the host int `len`, the
+    number of rows in use. The capacity is fixed here; an append past it
+    raises and never reallocates. The length is the same for every batch
+    row (all generate() needs): per-row lengths are not supported, and
+    neither is graph capture, since `len` lives on the host.
+
+    fp16 on a GPU is stored in bf16, the type the kernels compute in."""
+
+    def __init__(self, batch, capacity, kvheads, head_dim, dtype, device):
+        device = torch.device(device)
+        if dtype == torch.float16 and device.type == "cuda":
+            dtype = torch.bfloat16
+        self.k = torch.empty(batch, capacity, kvheads, head_dim, dtype=dtype,
+                             device=device)
+        self.v = torch.empty_like(self.k)
+        self.len = 0
+        self._cat = {}      # the FMS_AMD_DECODE=sdpa route's grown tensors
+
+    @property
+    def capacity(self):
+        return self.k.shape[1]
+
+
+def _decode_no_grad(*tensors):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError(
+            "the KV-cache ops have no backward: call them under "
+            "torch.no_grad() or with inputs that do not require grad")
+
+
+def _append_view(t):
+    """What kv_append_kernel reads without a copy: (b, s, h, d) with
+    contiguous heads, one uniform distance between the (b, s) rows (taken
+    from b at s == 1, where a fused-projection slice reports an arbitrary
+    s stride) and a row stride and base that keep 16-byte alignment."""
+    b, s, h, d = t.shape
+    rs = t.stride(1) if s > 1 else (t.stride(0) if b > 1 else h * d)
+    ok = (t.stride(3) == 1 and t.stride(2) == d and rs >= h * d
+          and (s == 1 or b == 1 or t.stride(0) == s * rs)
+          and rs % 8 == 0 and t.data_ptr() % 16 == 0)
+    return t if ok else t.contiguous()
+
+
+def kv_cache_append(cache, q, k, v, cos=None, sin=None):
+    """Append s positions to the cache in place: q (b,s,h,d), k/v
+    (b,s,kvh,d), all three possibly last-dim slices of the fused qkv
+    projection. With cos/sin (the table rows of positions [len, len+s)) q
+    and k are rotated; rotated k and raw v land in cache rows
+    [len, len+s), `len` advances and the rotated q comes back contiguous.
+    Without tables (learned positions) it only appends and returns q."""
+    _decode_no_grad(q, k, v)
+    s = q.shape[1]
+    if cache.len + s > cache.capacity:
+        raise ValueError(
+            f"KVCache overflow: {cache.len} + {s} rows exceed the capacity "
+            f"{cache.capacity}")
+    if q.is_cuda and q.dtype == torch.float16:
+        qr = kv_cache_append(cache, q.bfloat16(), k.bfloat16(), v.bfloat16(),
+                             cos, sin)
+        return qr.half()
+    if q.is_cuda and q.dtype == torch.bfloat16:
+        ext = _require_ext("kv_cache_append")
+        if cos is not None:
+            cos = cos.float().contiguous()
+            sin = sin.float().contiguous()
+        qr = ext.kv_append(_append_view(q), _append_view(k), _append_view(v),
+                           cache.k, cache.v, cache.len, cos, sin)
+        if cos is None:
+            qr = q
+    else:
+        qr = reference.kv_cache_append(cache.k, cache.v, cache.len, q, k, v,
+                                       cos, sin)
+    cache.len += s
+    return qr
+
+
+def attention_decode(q, cache):
+    """q (b,1,h,d) attends to cache rows [0, len). The newest key is
+    already inside, so there is no causal mask."""
+    _decode_no_grad(q)
+    if q.shape[1] != 1:
+        raise ValueError("attention_decode takes one query position")
+    if cache.len < 1:
+        raise ValueError("attention_decode on an empty cache")
+    if q.is_cuda and q.dtype == torch.float16:
+        return attention_decode(q.bfloat16(), cache).half()
+    if q.is_cuda and q.dtype == torch.bfloat16:
+        if os.environ.get("FMS_AMD_ALLOW_TORCH_SDPA") == "1":
+            import torch.nn.functional as F
+            n = cache.len
+            o = F.scaled_dot_product_attention(
+                q.transpose(1, 2), cache.k[:, :n].transpose(1, 2),
+                cache.v[:, :n].transpose(1, 2),
+                enable_gqa=(cache.k.shape[2] != q.shape[2]))
+            return o.transpose(1, 2)
+        ext = _require_ext("attention_decode")
+        o, _ = ext.attn_decode(q.contiguous(), cache.k, cache.v, cache.len, 0)
+        return o
+    return reference.attention_decode(q, cache.k, cache.v, cache.len)
+
+
+def _attention_cached_sdpa(q, k, v, cache, cos, sin):
+    """FMS_AMD_DECODE=sdpa: the former route (rope, torch.cat-grown K/V,
+    torch SDPA), kept for same-process A/B against the kernels."""
+    import torch.nn.functional as F
+    if cos is not None:
+        q, k = rope_apply(q, k, cos, sin)
+    if cache._cat.get("k") is not None:
+        k = torch.cat([cache._cat["k"], k], dim=1)
+        v = torch.cat([cache._cat["v"], v], dim=1)
+    cache._cat["k"], cache._cat["v"] = k, v
+    cache.len = k.shape[1]
+    o = F.scaled_dot_product_attention(
+        q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
+        is_causal=(q.shape[1] == k.shape[1]),
+        enable_gqa=(k.shape[2] != q.shape[2]))
+    return o.transpose(1, 2)
+
+
+def attention_cached(q, k, v, cache, cos=None, sin=None):
+    """Attention of s new positions over a KVCache: append (with RoPE when
+    tables are given), then
+      - prefill (the cache was empty): attention_causal on views of the
+        cache rows just written;
+      - s == 1: attention_decode;
+      - s > 1 on a non-empty cache (chunked prefill): the fp32 reference
+        with the causal mask aligned bottom right. Rare; correct, not
+        fast.
+    No backward (inference only)."""
+    _decode_no_grad(q, k, v)
+    if os.environ.get("FMS_AMD_DECODE") == "sdpa":
+        return _attention_cached_sdpa(q, k, v, cache, cos, sin)
+    if q.is_cuda and q.dtype == torch.float16:
+        return attention_cached(q.bfloat16(), k.bfloat16(), v.bfloat16(),
+                                cache, cos, sin).half()
+    was_empty = cache.len == 0
+    s = q.shape[1]
+    qr = kv_cache_append(cache, q, k, v, cos, sin)
+    if s == 1:
+        return attention_decode(qr, cache)
+    n = cache.len
+    if was_empty:
+        return attention_causal(qr, cache.k[:, :n], cache.v[:, :n])
+    return reference.attention_cached(qr, cache.k[:, :n], cache.v[:, :n])
+
+
 def attn_bwd_workspace_limit(mb=None):
     """Get/set the largest dS workspace (MiB) the attention backward may
     allocate; larger shapes run the O(s)-memory recompute path. 0 = never

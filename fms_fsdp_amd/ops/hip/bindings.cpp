@@ -8,6 +8,7 @@
 #include <tuple>
 #include <vector>
 
+#include "attn_decode_plan.h"
 #include "attn_ws.h"
 
 using torch::Tensor;
@@ -53,6 +54,13 @@ void launch_attn_bwd_doc(const void*, const void*, const void*, const void*,
                          int, float, int, long long, long long, hipStream_t);
 void launch_attn_bwd_delta(const void*, const void*, float*, int, int, int,
                            int, hipStream_t);
+void launch_kv_append(const void*, const void*, const void*, void*, void*,
+                      void*, const float*, const float*, int, int, int, int,
+                      int, long long, long long, long long, long long,
+                      long long, hipStream_t);
+void launch_attn_decode(const void*, const void*, const void*, void*, float*,
+                        float*, float*, int, int, int, int, int, long long,
+                        int, float, hipStream_t);
 int attn_sched_mode(int);
 int attn_dkv_mode(int);
 long long attn_bwd_ws_limit(long long);
@@ -476,6 +484,166 @@ std::tuple<Tensor, Tensor> attn_fwd(Tensor q, Tensor k, Tensor v) {
   launch_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
                   lse.data_ptr<float>(), b, s, h, kvh, d, scale, vs,
                   cur_stream());
+  return {o, lse};
+}
+
+// ---- KV-cache decode (attn_decode.hip) --------------------------------
+static bool aligned16(const Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// k/v cache pair: contiguous bf16 (b, capacity, kvh, d) on `dev`
+static void check_kv_cache(const Tensor& kcache, const Tensor& vcache,
+                           const torch::Device& dev) {
+  TORCH_CHECK(kcache.scalar_type() == torch::kBFloat16 &&
+                  vcache.scalar_type() == torch::kBFloat16,
+              "the kv cache must be bf16");
+  TORCH_CHECK(kcache.is_cuda() && vcache.is_cuda() &&
+                  kcache.device() == dev && vcache.device() == dev,
+              "the kv cache must live on q's GPU");
+  TORCH_CHECK(kcache.dim() == 4 && kcache.sizes() == vcache.sizes(),
+              "k and v cache must both be (b, capacity, kvh, d)");
+  TORCH_CHECK(kcache.is_contiguous() && vcache.is_contiguous(),
+              "the kv cache must be contiguous");
+  TORCH_CHECK(aligned16(kcache) && aligned16(vcache),
+              "the kv cache must be 16-byte aligned");
+}
+
+// Row stride of a (b, s, h, d) bf16 view with contiguous heads whose
+// (b, s) rows sit at one uniform distance. Unlike row_stride4 this takes
+// the stride from whichever of b and s has more than one entry: at s == 1
+// (every decode step) a slice of the fused projection reports an arbitrary
+// stride(1).
+static long long append_row_stride(const Tensor& t) {
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, "expected bf16");
+  TORCH_CHECK(t.dim() == 4 && t.stride(3) == 1 && t.stride(2) == t.size(3),
+              "expected a (b,s,h,d) view with contiguous heads");
+  const int64_t hd = t.size(2) * t.size(3);
+  int64_t rs = hd;
+  if (t.size(1) > 1) {
+    rs = t.stride(1);
+    TORCH_CHECK(t.size(0) <= 1 || t.stride(0) == t.size(1) * rs,
+                "expected a uniform (b, s) row stride");
+  } else if (t.size(0) > 1) {
+    rs = t.stride(0);
+  }
+  TORCH_CHECK(rs >= hd, "expected non-overlapping (b, s) rows");
+  return rs;
+}
+
+// Rotate q and k by the (s, d/2) fp32 tables (rows = the positions being
+// written), write rotated k and raw v into cache rows [pos, pos + s) and
+// return contiguous rotated q: split + rope + append in one launch.
+// Without tables only k and v are copied and q comes back as it is.
+// q (b,s,h,d), k/v (b,s,kvh,d): row-strided bf16 views (fused-qkv slices).
+Tensor kv_append(Tensor q, Tensor k, Tensor v, Tensor kcache, Tensor vcache,
+                 int64_t pos, c10::optional<Tensor> cos,
+                 c10::optional<Tensor> sin) {
+  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda() &&
+                  k.device() == q.device() && v.device() == q.device(),
+              "kv_append: q, k, v must be on one GPU");
+  const long long qs = append_row_stride(q), ks = append_row_stride(k),
+                  vs = append_row_stride(v);
+  check_kv_cache(kcache, vcache, q.device());
+  const int64_t b = q.size(0), s = q.size(1), h = q.size(2), d = q.size(3);
+  const int64_t kvh = k.size(2), cap = kcache.size(1);
+  TORCH_CHECK(k.size(0) == b && k.size(1) == s && k.size(3) == d &&
+                  v.sizes() == k.sizes(),
+              "kv_append: k and v must be (b, s, kvh, d) with q's b, s, d");
+  TORCH_CHECK(kcache.size(0) == b && kcache.size(2) == kvh &&
+                  kcache.size(3) == d,
+              "kv_append: cache shape does not match k");
+  TORCH_CHECK(d % 8 == 0, "kv_append: head_dim must be a multiple of 8");
+  TORCH_CHECK(pos >= 0 && pos + s <= cap, "kv_append: rows [", pos, ", ",
+              pos + s, ") do not fit the capacity ", cap);
+  TORCH_CHECK(qs % 8 == 0 && ks % 8 == 0 && vs % 8 == 0,
+              "kv_append: row strides must be multiples of 8 elements");
+  TORCH_CHECK(aligned16(q) && aligned16(k) && aligned16(v),
+              "kv_append: q, k, v must be 16-byte aligned");
+  TORCH_CHECK(cos.has_value() == sin.has_value(),
+              "kv_append: cos and sin come together");
+  TORCH_CHECK(b * s * (h + 2 * kvh) * d / 8 < (1LL << 31) * 256,
+              "kv_append: too many elements for one grid");
+  const float *cp = nullptr, *sp = nullptr;
+  if (cos.has_value()) {
+    for (const Tensor* t : {&*cos, &*sin})
+      TORCH_CHECK(t->scalar_type() == torch::kFloat32 && t->is_contiguous() &&
+                      t->is_cuda() && t->device() == q.device() &&
+                      t->dim() == 2 && t->size(0) == s &&
+                      t->size(1) == d / 2 && aligned16(*t),
+                  "kv_append: cos/sin must be contiguous fp32 (s, d/2) "
+                  "tables with one row per appended position");
+    cp = cos->data_ptr<float>();
+    sp = sin->data_ptr<float>();
+  }
+  if (b == 0 || s == 0) return q;
+  Tensor qo = cp ? torch::empty({b, s, h, d}, q.options()) : q;
+  launch_kv_append(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                   cp ? qo.data_ptr() : nullptr, kcache.data_ptr(),
+                   vcache.data_ptr(), cp, sp, (int)b, (int)s, (int)h,
+                   (int)kvh, (int)d, qs, ks, vs, cap, pos, cur_stream());
+  return qo;
+}
+
+// Split count attn_decode picks for (b, kvh, kv_len) on n_cu compute units.
+int64_t attn_decode_plan_py(int64_t b, int64_t kvh, int64_t kv_len,
+                            int64_t n_cu) {
+  return attn_decode_plan(b, kvh, kv_len, n_cu);
+}
+
+// q (b, 1, h, d) against cache rows [0, kv_len): (o (b,1,h,d) bf16,
+// lse (b, h) fp32, natural log). The newest key is already in the cache,
+// so there is no causal mask. splits = 0 takes attn_decode_plan's count, a
+// positive value forces it; either is clamped to the number of key tiles.
+// splits > 1 allocates the fp32 partial workspace for this call.
+std::tuple<Tensor, Tensor> attn_decode(Tensor q, Tensor kcache, Tensor vcache,
+                                       int64_t kv_len, int64_t splits) {
+  TORCH_CHECK(q.is_cuda(), "attn_decode: q must be on a GPU");
+  CHECK_BF16_CONTIG(q);
+  check_kv_cache(kcache, vcache, q.device());
+  TORCH_CHECK(q.dim() == 4 && q.size(1) == 1,
+              "attn_decode: q must be (b, 1, h, d)");
+  const int64_t b = q.size(0), h = q.size(2), d = q.size(3);
+  const int64_t cap = kcache.size(1), kvh = kcache.size(2);
+  TORCH_CHECK(kcache.size(0) == b && kcache.size(3) == d,
+              "attn_decode: cache shape does not match q");
+  TORCH_CHECK(d == 64 || d == 128, "attn_decode: head_dim must be 64 or 128");
+  TORCH_CHECK(kv_len >= 1 && kv_len <= cap, "attn_decode: kv_len ", kv_len,
+              " outside [1, capacity ", cap, "]");
+  TORCH_CHECK(kvh >= 1 && h % kvh == 0,
+              "attn_decode: kvheads must divide nheads");
+  TORCH_CHECK(h / kvh <= 64,
+              "attn_decode: at most 64 query heads per kv head");
+  TORCH_CHECK(aligned16(q), "attn_decode: q must be 16-byte aligned");
+  TORCH_CHECK(splits >= 0, "attn_decode: splits must be >= 0");
+  TORCH_CHECK(kv_len < (1LL << 31) - 64, "attn_decode: kv_len too large");
+  auto o = torch::empty_like(q);
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto lse = torch::empty({b, h}, f32);
+  if (b == 0) return {o, lse};
+  if (splits == 0) {
+    int n_cu = 0;
+    TORCH_CHECK(hipDeviceGetAttribute(&n_cu,
+                                      hipDeviceAttributeMultiprocessorCount,
+                                      q.get_device()) == hipSuccess,
+                "attn_decode: cannot query the compute unit count");
+    splits = attn_decode_plan(b, kvh, kv_len, n_cu);
+  }
+  splits = attn_decode_clamp_splits(splits, kv_len);
+  const int64_t ncb = (h / kvh + 31) / 32;
+  TORCH_CHECK(b * kvh * ncb * splits < (1LL << 31),
+              "attn_decode: too many workgroups for one grid");
+  Tensor ws_o, ws_ml;
+  if (splits > 1) {
+    ws_o = torch::empty({b, h, splits, d}, f32);
+    ws_ml = torch::empty({b, h, splits, 2}, f32);
+  }
+  launch_attn_decode(q.data_ptr(), kcache.data_ptr(), vcache.data_ptr(),
+                     o.data_ptr(), lse.data_ptr<float>(),
+                     splits > 1 ? ws_o.data_ptr<float>() : nullptr,
+                     splits > 1 ? ws_ml.data_ptr<float>() : nullptr, (int)b,
+                     (int)h, (int)kvh, (int)d, (int)kv_len, cap, (int)splits,
+                     1.f / sqrtf((float)d), cur_stream());
   return {o, lse};
 }
 
@@ -929,6 +1097,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ssd_ygate_bwd", &ssd_ygate_bwd);
   mod.def("attn_fwd", &attn_fwd);
   mod.def("attn_bwd", &attn_bwd);
+  mod.def("kv_append", &kv_append, pybind11::arg("q"), pybind11::arg("k"),
+          pybind11::arg("v"), pybind11::arg("kcache"),
+          pybind11::arg("vcache"), pybind11::arg("pos"),
+          pybind11::arg("cos") = pybind11::none(),
+          pybind11::arg("sin") = pybind11::none());
+  mod.def("attn_decode", &attn_decode, pybind11::arg("q"),
+          pybind11::arg("kcache"), pybind11::arg("vcache"),
+          pybind11::arg("kv_len"), pybind11::arg("splits") = 0);
+  mod.def("attn_decode_plan", &attn_decode_plan_py);
   mod.def("attn_bwd_delta", &attn_bwd_delta);
   mod.def("attn_fwd_doc", &attn_fwd_doc);
   mod.def("attn_bwd_doc", &attn_bwd_doc);

@@ -57,6 +57,46 @@ def attention_causal(q, k, v, doc_mask=None):
     return o.transpose(1, 2).to(q.dtype)
 
 
+def kv_cache_append(kcache, vcache, pos, q, k, v, cos=None, sin=None):
+    """Rotate q and k by the tables of the positions being written (none:
+    learned positions, nothing to rotate), store k and raw v in cache rows
+    [pos, pos + s) in place and return q. Caches (b, capacity, kvh, d)."""
+    if cos is not None:
+        q, k = rope_apply(q, k, cos, sin)
+    s = k.shape[1]
+    kcache[:, pos:pos + s] = k
+    vcache[:, pos:pos + s] = v
+    return q
+
+
+def attention_cached(q, k, v):
+    """q (b,s,h,d) = the LAST s positions of the k/v (b,n,kvh,d) it attends
+    to, n >= s: query i sees keys j <= n - s + i (causal, aligned bottom
+    right). s == n is causal attention, s == 1 decode (no mask at all)."""
+    b, s, h, d = q.shape
+    n, kvh = k.shape[1], k.shape[2]
+    qt = q.transpose(1, 2).float()
+    kt = k.transpose(1, 2).float()
+    vt = v.transpose(1, 2).float()
+    if s == n:
+        o = F.scaled_dot_product_attention(qt, kt, vt, is_causal=True,
+                                           enable_gqa=(kvh != h))
+    elif s == 1:
+        o = F.scaled_dot_product_attention(qt, kt, vt, enable_gqa=(kvh != h))
+    else:
+        mask = torch.ones(s, n, dtype=torch.bool, device=q.device) \
+            .tril(diagonal=n - s)
+        o = F.scaled_dot_product_attention(qt, kt, vt, attn_mask=mask,
+                                           enable_gqa=(kvh != h))
+    return o.transpose(1, 2).to(q.dtype)
+
+
+def attention_decode(q, kcache, vcache, kv_len):
+    """q (b,1,h,d) against cache rows [0, kv_len); the newest key is
+    already inside, so nothing is masked."""
+    return attention_cached(q, kcache[:, :kv_len], vcache[:, :kv_len])
+
+
 def swiglu(gu):
     """gu (..., 2H) fused gate|up -> silu(g) * u, (..., H)."""
     g, u = gu.float().chunk(2, dim=-1)
