@@ -109,8 +109,10 @@ class train_config:
     # limit the O(s)-memory recompute backward runs instead (about 7/5 of
     # the gemm work). 0 = never use the workspace.
     attn_bwd_workspace_mb: int = 4096
-    # Mask attention at document boundaries of the packed rows: a token
-    # attends only to its own document (the one its row's previous
-    # `eos_token` closed). Llama only; the masked backward always runs the
-    # O(s)-memory kernels, whatever attn_bwd_workspace_mb says.
+    # Keep every token of a packed row inside its own document (the one
+    # its row's previous `eos_token` closed). Llama: attention is masked at
+    # the document boundaries; the masked backward always runs the
+    # O(s)-memory kernels, whatever attn_bwd_workspace_mb says. Mamba2 and
+    # the hybrid: the SSM state and the causal conv restart at every
+    # document start, and the hybrid's attention layers take the same mask.
     doc_mask: bool = False

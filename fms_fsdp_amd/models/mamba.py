@@ -73,12 +73,39 @@ def segsum(x):
     return out.masked_fill(~mask, -torch.inf)
 
 
-def ssd_chunked(x, dt, A, B, C, chunk):
+def doc_chunk_keep(doc_start, chunk):
+    """(b, l) document starts -> (b, nc, nc) bool over the inter-chunk
+    decay matrix W: entry [z, c] (z >= c) carries the state chunk c hands
+    on to the end of chunk z. It survives iff the last token of chunk z
+    still belongs to the document of the last token of chunk c, i.e.
+    start[(z+1)Q - 1] <= (c+1)Q - 1."""
+    b, l = doc_start.shape
+    last = torch.arange(chunk - 1, l, chunk, device=doc_start.device)  # (nc)
+    return doc_start.long()[:, last][:, :, None] <= last[None, None, :]
+
+
+def _doc_rel_start(doc_start, chunk):
+    """(b, nc, Q): document start of every token relative to the first
+    position of its chunk (negative: it began in an earlier chunk)."""
+    b, l = doc_start.shape
+    first = torch.arange(l, device=doc_start.device) // chunk * chunk
+    return (doc_start.long() - first).view(b, l // chunk, chunk)
+
+
+def ssd_chunked(x, dt, A, B, C, chunk, doc_start=None):
     """State-space dual scan (fp32 math).
 
     x (b,l,h,p), dt (b,l,h) [already softplus'ed], A (h) [negative],
     B/C (b,l,g,n). Returns y (b,l,h,p). Exact parallel-chunk algorithm:
     diagonal blocks via masked C B^T, inter-chunk state recurrence.
+
+    doc_start (b,l) (ops.DocMask.start): the state is reset at every
+    document start of a packed row, y_i = sum over start[i] <= j <= i.
+    Four selects to exact 0 on the decay factors: the intra-chunk L, the
+    decay into the chunk-final state (only the chunk's last document feeds
+    it), the inter-chunk W (doc_chunk_keep) and the decay out of the
+    carried state (only tokens whose document began before their chunk
+    read it).
     """
     b, l, h, p = x.shape
     g, n = B.shape[2], B.shape[3]
@@ -111,6 +138,11 @@ def ssd_chunked(x, dt, A, B, C, chunk):
     # kernel pass (ops/hip/ssd.hip).
     from fms_fsdp_amd.ops import segsum_exp
     L = segsum_exp(dA_cs).to(mm_dtype)               # (b,nc,h,Q,Q)
+    if doc_start is not None:
+        rel = _doc_rel_start(doc_start, chunk)       # (b,nc,Q)
+        qpos = torch.arange(chunk, device=x.device)
+        inside = qpos >= rel[..., None]              # (b,nc,Q,Q): j >= rel_i
+        L = torch.where(inside[:, :, None], L, torch.zeros_like(L))
     scores_g = torch.einsum("bcqgn,bckgn->bcgqk", Cm, Bm)  # (b,nc,g,Q,Q)
     sL = scores_g.view(b, nc, g, 1, chunk, chunk) * \
         L.view(b, nc, g, rep, chunk, chunk)
@@ -125,6 +157,10 @@ def ssd_chunked(x, dt, A, B, C, chunk):
     # — the decay is per-head, so fold it into xdt instead of
     # materializing a decayed copy of B over all heads
     decay_states = torch.exp(dA_cs[..., -1:] - dA_cs)           # (b,nc,h,Q)
+    if doc_start is not None:
+        decay_states = torch.where((qpos >= rel[..., -1:])[:, :, None],
+                                   decay_states,
+                                   torch.zeros_like(decay_states))
     xdt_dec = xdt_m * decay_states.permute(0, 1, 3, 2) \
         .unsqueeze(-1).to(mm_dtype)
     states = torch.einsum(
@@ -138,6 +174,9 @@ def ssd_chunked(x, dt, A, B, C, chunk):
     # Python loop (which cost thousands of tiny kernel launches).
     G = dA_cs[..., -1].permute(0, 2, 1)                         # (b,h,nc)
     W = torch.exp(segsum(G))                                    # (b,h,nc,nc)
+    if doc_start is not None:
+        W = torch.where(doc_chunk_keep(doc_start, chunk)[:, None], W,
+                        torch.zeros_like(W))
     # shift the tiny decay matrix, not the big states tensor
     Wsh = torch.cat([torch.zeros_like(W[:, :, :1]), W[:, :, :-1]], dim=2)
     prev_states = torch.einsum("bhzc,bchnp->bzhnp", Wsh, states)  # (b,nc,h,n,p)
@@ -146,6 +185,9 @@ def ssd_chunked(x, dt, A, B, C, chunk):
     # group; the per-(q,h) decay multiplies the GEMM OUTPUT (size h*p)
     # instead of a materialized decayed C copy (size h*n)
     state_decay = torch.exp(dA_cs)                              # (b,nc,h,Q)
+    if doc_start is not None:
+        state_decay = torch.where((rel < 0)[:, :, None], state_decay,
+                                  torch.zeros_like(state_decay))
     y_off = torch.einsum(
         "bcqgn,bcgrnp->bcqgrp", Cm,
         prev_states.view(b, nc, g, rep, n, p).to(mm_dtype)).float() \
@@ -199,14 +241,20 @@ class Mamba2Mixer(nn.Module):
         nn.init.ones_(self.D)
         self.norm.reset_parameters()
 
-    def _scan_fused(self, b, l, x, dt, z, B, C, dtb, Alog, D_):
+    def _scan_fused(self, b, l, x, dt, z, B, C, dtb, Alog, D_,
+                    doc_start=None, doc_end=None):
         """GPU SSD scan: the elementwise chains run as fused HIP kernels
         (ops/hip/ssd.hip — prep/xdt/scores-decay/ygate, each with a
         custom backward); only the MFMA-shaped work (scores, y_diag,
         states, y_off einsums on hipBLASLt) and the tiny nc x nc
         inter-chunk recurrence stay as torch ops. Inputs x/dt/z/B/C are
         STRIDED slices of the fused projections — no contiguous copies.
-        Returns the gated (b, l, d_inner) bf16 activations (pre-norm)."""
+        Returns the gated (b, l, d_inner) bf16 activations (pre-norm).
+        doc_start/doc_end (a DocMask's arrays) reset the scan at every
+        document start: masked xdt / scores-decay / ygate kernels plus a
+        select on the inter-chunk matrix (see ssd_chunked)."""
+        doc_mask = None if doc_start is None else ops.DocMask(doc_start,
+                                                              doc_end)
         h, p = self.nheads, self.headdim
         g, n = self.ngroups, self.d_state
         Q = self.chunk
@@ -218,14 +266,16 @@ class Mamba2Mixer(nn.Module):
         dtf, dacs = ops.ssd_prep(dt2, dtb, Alog, Q)        # (b*nc*h, Q) fp32
         # xdt/xdtd come out H-MAJOR (b,nc,h,Q,p): y_diag is then a plain
         # strided-batched bmm and no einsum materializes permuted copies
-        xdt, xdtd = ops.ssd_xdt(x2, dtf, dacs, h, p, Q)    # bf16 pair
+        xdt, xdtd = ops.ssd_xdt(x2, dtf, dacs, h, p, Q,    # bf16 pair
+                                doc_mask=doc_mask)
         N = b * nc * h
         Bm = B.reshape(b, nc, Q, g, n)
         Cm = C.reshape(b, nc, Q, g, n)
         # scores per GROUP (g << h), decay folded in-kernel (L never
         # materialized; d_scores comes back from the fused backward)
         scores = torch.einsum("bcqgn,bckgn->bcgqk", Cm, Bm).contiguous()
-        sL = ops.ssd_scores_decay(dacs, scores.view(b * nc * g, Q, Q), h, g)
+        sL = ops.ssd_scores_decay(dacs, scores.view(b * nc * g, Q, Q), h, g,
+                                  doc_mask=doc_mask)
         y_diag = torch.bmm(sL, xdt.view(N, Q, p))          # (N, Q, p) bf16
         # the whole inter-chunk state chain runs bf16 (W entries are
         # decays in [0,1], states are sums of bf16-rounded products with
@@ -239,6 +289,9 @@ class Mamba2Mixer(nn.Module):
         # (zero first row) instead of a 167 MB cat on the states tensor.
         G = dacs.view(b, nc, h, Q)[..., -1].permute(0, 2, 1)
         W = torch.exp(segsum(G))
+        if doc_start is not None:
+            W = torch.where(doc_chunk_keep(doc_start, Q)[:, None], W,
+                            torch.zeros_like(W))
         Wsh = torch.cat([torch.zeros_like(W[:, :, :1]), W[:, :, :-1]],
                         dim=2).to(torch.bfloat16)
         prev = torch.einsum("bhzc,bchnp->bzhnp", Wsh, states)
@@ -250,17 +303,22 @@ class Mamba2Mixer(nn.Module):
         out = ops.ssd_ygate(
             y_diag.reshape(b * l, h * p),
             y_off.contiguous().view(b * l, h * p),
-            dacs, x2, D_, z2, h, g, p, Q)
+            dacs, x2, D_, z2, h, g, p, Q, doc_mask=doc_mask)
         return out.view(b, l, h * p)
 
-    def forward(self, u):
+    def forward(self, u, doc_mask=None):
+        """doc_mask (ops.DocMask): conv and SSM state restart at every
+        document of a packed row."""
         b, l, _ = u.shape
         zxbcdt = ops.linear_flat(u, self.in_proj.weight)
         z, xBC, dt = torch.split(
             zxbcdt, [self.d_inner, self.conv_dim, self.nheads], dim=-1)
 
         # causal depthwise conv + silu (fp32 math)
-        xBC = ops.causal_conv1d(xBC, self.conv_weight, self.conv_bias)
+        xBC = ops.causal_conv1d(xBC, self.conv_weight, self.conv_bias,
+                                doc_mask=doc_mask)
+        # the mask's arrays are plain extra inputs of the checkpointed scan
+        doc = () if doc_mask is None else (doc_mask.start, doc_mask.end)
 
         x, B, C = torch.split(
             xBC, [self.d_inner,
@@ -270,7 +328,8 @@ class Mamba2Mixer(nn.Module):
         if u.is_cuda and u.dtype == torch.bfloat16 and l % self.chunk == 0 \
                 and not getattr(self, "_force_torch_scan", False) \
                 and os.environ.get("FMS_AMD_FORCE_TORCH_SCAN") != "1":
-            args = (b, l, x, dt, z, B, C, self.dt_bias, self.A_log, self.D)
+            args = (b, l, x, dt, z, B, C, self.dt_bias, self.A_log,
+                    self.D) + doc
             if torch.is_grad_enabled() and self.training:
                 y = torch.utils.checkpoint.checkpoint(
                     self._scan_fused, *args, use_reentrant=False)
@@ -279,7 +338,8 @@ class Mamba2Mixer(nn.Module):
             y = self.norm(y)
             return ops.linear_flat(y, self.out_proj.weight)
 
-        def _scan(x_, dt_, dtb, Alog, B_, C_, D_):
+        def _scan(x_, dt_, dtb, Alog, B_, C_, D_, doc_start=None,
+                  doc_end=None):
             # fp32 SSD; recomputed in backward (the chunked intermediates
             # -- L, scores, states -- are large and cheap to rebuild)
             dtf = F.softplus(dt_.float() + dtb.float())
@@ -288,15 +348,15 @@ class Mamba2Mixer(nn.Module):
             y_ = ssd_chunked(xh, dtf, A,
                              B_.view(b, l, self.ngroups, self.d_state).float(),
                              C_.view(b, l, self.ngroups, self.d_state).float(),
-                             self.chunk)
+                             self.chunk, doc_start=doc_start)
             return y_ + xh * D_.view(1, 1, -1, 1)
 
         if torch.is_grad_enabled() and self.training:
             y = torch.utils.checkpoint.checkpoint(
-                _scan, x, dt, self.dt_bias, self.A_log, B, C, self.D,
+                _scan, x, dt, self.dt_bias, self.A_log, B, C, self.D, *doc,
                 use_reentrant=False)
         else:
-            y = _scan(x, dt, self.dt_bias, self.A_log, B, C, self.D)
+            y = _scan(x, dt, self.dt_bias, self.A_log, B, C, self.D, *doc)
         y = y.reshape(b, l, self.d_inner).to(u.dtype)
         y = self.norm(y * F.silu(z))
         return ops.linear_flat(y, self.out_proj.weight)
@@ -333,7 +393,7 @@ class MambaAttnMixer(nn.Module):
         if self.proj.bias is not None:
             nn.init.zeros_(self.proj.bias)
 
-    def forward(self, x):
+    def forward(self, x, doc_mask=None):
         b, s, _ = x.shape
         qkv = (self.qkv(x) if self.qkv.bias is not None
                else ops.linear_flat(x, self.qkv.weight))
@@ -350,7 +410,9 @@ class MambaAttnMixer(nn.Module):
                                     cos, sin)
             q = torch.cat([qr, q[..., self.rot_dim:]], dim=-1)
             k = torch.cat([kr, k[..., self.rot_dim:]], dim=-1)
-        o = ops.attention_causal(q.contiguous(), k.contiguous(), v.contiguous())
+        # rotary positions are not reset per document (as in Llama)
+        o = ops.attention_causal(q.contiguous(), k.contiguous(),
+                                 v.contiguous(), doc_mask=doc_mask)
         o2 = o.reshape(b, s, -1)
         if self.proj.bias is not None:
             return self.proj(o2)
@@ -400,14 +462,14 @@ class MambaBlock(nn.Module):
             self.norm2.reset_parameters()
             self.mlp.reset_parameters()
 
-    def forward(self, x):
+    def forward(self, x, doc_mask=None):
         if getattr(self, "_ac_enabled", False) and torch.is_grad_enabled():
             return torch.utils.checkpoint.checkpoint(
-                self._forward_impl, x, use_reentrant=False)
-        return self._forward_impl(x)
+                self._forward_impl, x, doc_mask, use_reentrant=False)
+        return self._forward_impl(x, doc_mask)
 
-    def _forward_impl(self, x):
-        h = self.mixer(self.norm(x))
+    def _forward_impl(self, x, doc_mask=None):
+        h = self.mixer(self.norm(x), doc_mask=doc_mask)
         if self.mlp is not None:
             # fused residual-add + norm (the reference's fused_add_norm,
             # config_utils.py:182 there)
@@ -427,6 +489,10 @@ class MambaLMHeadModel(nn.Module):
         self.lm_head = nn.Linear(cfg.d_model, cfg.vocab_size, bias=False)
         if cfg.tie_embeddings:
             self.lm_head.weight = self.embedding.weight
+        # token id that ends a packed document; when set, forward() keeps
+        # conv, SSM state and attention inside each document (config knob
+        # `doc_mask`)
+        self.doc_mask_token = None
 
     def reset_parameters(self):
         nn.init.trunc_normal_(self.embedding.weight, std=0.02)
@@ -436,10 +502,17 @@ class MambaLMHeadModel(nn.Module):
         for l in self.layers:
             l.reset_parameters()
 
-    def forward(self, tokens, labels=None):
+    def forward(self, tokens, labels=None, doc_mask=None):
+        """doc_mask (ops.DocMask) keeps every layer inside each document
+        of a packed row: the causal conv and the SSM state restart at a
+        document's first token and the hybrid's attention layers mask
+        across documents. With `doc_mask_token` set it is built from
+        `tokens`, once per forward, and shared by all layers."""
+        if doc_mask is None and self.doc_mask_token is not None:
+            doc_mask = ops.doc_mask_from_tokens(tokens, self.doc_mask_token)
         x = self.embedding(tokens)
         for layer in self.layers:
-            x = layer(x)
+            x = layer(x, doc_mask=doc_mask)
         x = self.norm_f(x)
         if labels is not None:
             return ops.linear_cross_entropy(x, self.lm_head.weight, labels)

@@ -847,28 +847,48 @@ def linear_cross_entropy(x, weight, labels, ignore_index=-100):
 # Fused causal depthwise conv1d + silu (mamba xBC conv)
 # --------------------------------------------------------------------------
 class _CausalConv1dFn(torch.autograd.Function):
+    """With doc_start/doc_end (a DocMask's two arrays) the conv restarts
+    at every document of a packed row: the masked kernels."""
+
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, doc_start=None, doc_end=None):
         ext = _require_ext("causal_conv1d")
         x = x.contiguous()
         wb = weight.contiguous().bfloat16()
         bf = bias.float().contiguous()
-        y = ext.cconv_fwd(x, wb, bf)
-        ctx.save_for_backward(x, wb, bf)
+        if doc_start is None:
+            y = ext.cconv_fwd(x, wb, bf)
+            ctx.save_for_backward(x, wb, bf)
+        else:
+            y = ext.cconv_fwd_doc(x, wb, bf, doc_start)
+            ctx.save_for_backward(x, wb, bf, doc_start, doc_end)
         ctx.wdtype = weight.dtype
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, wb, bf = ctx.saved_tensors
-        dx, dw, db = _C.cconv_bwd(dy.contiguous(), x, wb, bf)
-        return dx, dw.to(ctx.wdtype), db.to(ctx.wdtype)
+        x, wb, bf, *doc = ctx.saved_tensors
+        if doc:
+            dx, dw, db = _C.cconv_bwd_doc(dy.contiguous(), x, wb, bf, *doc)
+        else:
+            dx, dw, db = _C.cconv_bwd(dy.contiguous(), x, wb, bf)
+        return dx, dw.to(ctx.wdtype), db.to(ctx.wdtype), None, None
 
 
-def causal_conv1d(x, weight, bias):
+def _doc_arrays(doc_mask):
+    """() for no mask, else the DocMask's contiguous (start, end)."""
+    if doc_mask is None:
+        return ()
+    return doc_mask.start.contiguous(), doc_mask.end.contiguous()
+
+
+def causal_conv1d(x, weight, bias, doc_mask=None):
+    """x (b, l, C). doc_mask (DocMask): a token's window stops at the
+    first token of its document instead of reaching into the previous
+    one."""
     if x.is_cuda and x.dtype == torch.bfloat16:
-        return _CausalConv1dFn.apply(x, weight, bias)
-    return reference.causal_conv1d(x, weight, bias)
+        return _CausalConv1dFn.apply(x, weight, bias, *_doc_arrays(doc_mask))
+    return reference.causal_conv1d(x, weight, bias, doc_mask)
 
 
 # --------------------------------------------------------------------------
@@ -906,7 +926,28 @@ def segsum_exp(cs):
 # hand-written selective-scan; reference reaches mamba_ssm's kernels from
 # main_training_mamba.py:8-9,67). GPU-only: the CPU path keeps the plain
 # torch ssd_chunked as the numerics oracle.
+#
+# xdt / scores_decay / ygate take an optional doc_mask (DocMask of the
+# (b, l) rows behind the flat b*l dimension): the scan then resets at
+# every document start (docs/kernels.md "Document mask"). Its start array
+# rides through the autograd functions as a non-differentiable input.
+# Tensors that are not on the GPU go to the float64-capable oracles of
+# ops/reference.py.
 # --------------------------------------------------------------------------
+def _doc_start_arg(doc_mask, rows, Q):
+    """() for no mask, else (start (b, l) int32 contiguous,) after checking
+    that its rows are the `rows` tokens, cut into chunks of Q."""
+    if doc_mask is None:
+        return ()
+    start = doc_mask.start.contiguous()
+    if start.numel() != rows or start.shape[-1] % Q:
+        raise ValueError(
+            f"doc_mask of shape {tuple(start.shape)} does not describe "
+            f"{rows} tokens in chunks of {Q}")
+    return (start,)
+
+
+
 class _SSDPrepFn(torch.autograd.Function):
     """(dt2d strided bf16 (b*l, H), dt_bias, A_log) ->
     dtf (N,Q) fp32, dacs (N,Q) fp32 with N=(b*l/Q)*H, n = bc*H + h:
@@ -942,28 +983,42 @@ class _SSDXdtFn(torch.autograd.Function):
     permute copies); xdt = x*dtf, decayed by exp(dacs_end-dacs)."""
 
     @staticmethod
-    def forward(ctx, x2d, dtf, dacs, H, P, Q):
+    def forward(ctx, x2d, dtf, dacs, H, P, Q, doc_start=None):
         ext = _require_ext("ssd_xdt")
-        xdt, xdtd = ext.ssd_xdt_fwd(x2d, dtf, dacs, H, P, Q)
-        ctx.save_for_backward(x2d, dtf, dacs)
+        if doc_start is None:
+            xdt, xdtd = ext.ssd_xdt_fwd(x2d, dtf, dacs, H, P, Q)
+            ctx.save_for_backward(x2d, dtf, dacs)
+        else:
+            xdt, xdtd = ext.ssd_xdt_fwd_doc(x2d, dtf, dacs, H, P, Q,
+                                            doc_start, doc_start.shape[-1])
+            ctx.save_for_backward(x2d, dtf, dacs, doc_start)
         ctx.meta = (H, P, Q)
         return xdt, xdtd
 
     @staticmethod
     def backward(ctx, dxdt, dxdtd):
-        x2d, dtf, dacs = ctx.saved_tensors
+        x2d, dtf, dacs, *doc = ctx.saved_tensors
         H, P, Q = ctx.meta
-        dx, ddtf, sdec = _C.ssd_xdt_bwd(
-            dxdt.contiguous(), dxdtd.contiguous(), x2d, dtf, dacs, H, P, Q)
+        if doc:
+            dx, ddtf, sdec = _C.ssd_xdt_bwd_doc(
+                dxdt.contiguous(), dxdtd.contiguous(), x2d, dtf, dacs, H, P,
+                Q, doc[0], doc[0].shape[-1])
+        else:
+            dx, ddtf, sdec = _C.ssd_xdt_bwd(
+                dxdt.contiguous(), dxdtd.contiguous(), x2d, dtf, dacs, H, P,
+                Q)
         # fold the decay-exponent grads: d/d dacs[q] = -sdec[q], and the
         # end column accumulates all q of its row
         ddacs = sdec.neg()
         ddacs[:, -1] += sdec.sum(-1)
-        return dx, ddtf, ddacs, None, None, None
+        return dx, ddtf, ddacs, None, None, None, None
 
 
-def ssd_xdt(x2d, dtf, dacs, H, P, Q):
-    return _SSDXdtFn.apply(x2d, dtf, dacs, H, P, Q)
+def ssd_xdt(x2d, dtf, dacs, H, P, Q, doc_mask=None):
+    if not x2d.is_cuda:
+        return reference.ssd_xdt(x2d, dtf, dacs, H, P, Q, doc_mask)
+    return _SSDXdtFn.apply(x2d, dtf, dacs, H, P, Q,
+                           *_doc_start_arg(doc_mask, x2d.shape[0], Q))
 
 
 class _SSDScoresDecayFn(torch.autograd.Function):
@@ -972,28 +1027,41 @@ class _SSDScoresDecayFn(torch.autograd.Function):
     backward returns per-head d_scores summed over each group's heads."""
 
     @staticmethod
-    def forward(ctx, dacs, scores3d, H, G):
+    def forward(ctx, dacs, scores3d, H, G, doc_start=None):
         ext = _require_ext("ssd_sl")
-        sL = ext.ssd_sl_fwd(dacs, scores3d, H, G)
-        ctx.save_for_backward(dacs, scores3d)
+        if doc_start is None:
+            sL = ext.ssd_sl_fwd(dacs, scores3d, H, G)
+            ctx.save_for_backward(dacs, scores3d)
+        else:
+            sL = ext.ssd_sl_fwd_doc(dacs, scores3d, H, G, doc_start,
+                                    doc_start.shape[-1])
+            ctx.save_for_backward(dacs, scores3d, doc_start)
         ctx.meta = (H, G)
         return sL
 
     @staticmethod
     def backward(ctx, g):
-        dacs, scores3d = ctx.saved_tensors
+        dacs, scores3d, *doc = ctx.saved_tensors
         H, G = ctx.meta
-        dsh, dcs = _C.ssd_sl_bwd(g.contiguous(), scores3d, dacs, H, G)
+        if doc:
+            dsh, dcs = _C.ssd_sl_bwd_doc(g.contiguous(), scores3d, dacs, H,
+                                         G, doc[0], doc[0].shape[-1])
+        else:
+            dsh, dcs = _C.ssd_sl_bwd(g.contiguous(), scores3d, dacs, H, G)
         rep = H // G
         M = scores3d.shape[0]
         Q = scores3d.shape[1]
         dscores = dsh.view(M // G, G, rep, Q, Q) \
             .sum(dim=2, dtype=torch.float32).to(scores3d.dtype).view(M, Q, Q)
-        return dcs, dscores, None, None
+        return dcs, dscores, None, None, None
 
 
-def ssd_scores_decay(dacs, scores3d, H, G):
-    return _SSDScoresDecayFn.apply(dacs, scores3d, H, G)
+def ssd_scores_decay(dacs, scores3d, H, G, doc_mask=None):
+    if not dacs.is_cuda:
+        return reference.ssd_scores_decay(dacs, scores3d, H, G, doc_mask)
+    N, Q = dacs.shape
+    return _SSDScoresDecayFn.apply(
+        dacs, scores3d, H, G, *_doc_start_arg(doc_mask, N // H * Q, Q))
 
 
 class _SSDYGateFn(torch.autograd.Function):
@@ -1001,29 +1069,48 @@ class _SSDYGateFn(torch.autograd.Function):
     (y assembly + D residual + the gated epilogue)."""
 
     @staticmethod
-    def forward(ctx, ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q):
+    def forward(ctx, ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q,
+                doc_start=None):
         ext = _require_ext("ssd_ygate")
         D_f = D.detach().float().contiguous()
-        out = ext.ssd_ygate_fwd(ydiag, yoff, dacs, x2d, D_f, z2d, H, G, P, Q)
-        ctx.save_for_backward(ydiag, yoff, dacs, x2d, D_f, z2d)
+        if doc_start is None:
+            out = ext.ssd_ygate_fwd(ydiag, yoff, dacs, x2d, D_f, z2d, H, G,
+                                    P, Q)
+            ctx.save_for_backward(ydiag, yoff, dacs, x2d, D_f, z2d)
+        else:
+            out = ext.ssd_ygate_fwd_doc(ydiag, yoff, dacs, x2d, D_f, z2d, H,
+                                        G, P, Q, doc_start,
+                                        doc_start.shape[-1])
+            ctx.save_for_backward(ydiag, yoff, dacs, x2d, D_f, z2d,
+                                  doc_start)
         ctx.meta = (H, G, P, Q, D.dtype)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        ydiag, yoff, dacs, x2d, D_f, z2d = ctx.saved_tensors
+        ydiag, yoff, dacs, x2d, D_f, z2d, *doc = ctx.saved_tensors
         H, G, P, Q, ddt = ctx.meta
-        dydiag, dyoff, ddacs, dx, dD_rows, dz = _C.ssd_ygate_bwd(
-            dout.contiguous(), ydiag, yoff, dacs, x2d, D_f, z2d, H, G, P, Q)
+        if doc:
+            dydiag, dyoff, ddacs, dx, dD_rows, dz = _C.ssd_ygate_bwd_doc(
+                dout.contiguous(), ydiag, yoff, dacs, x2d, D_f, z2d, H, G, P,
+                Q, doc[0], doc[0].shape[-1])
+        else:
+            dydiag, dyoff, ddacs, dx, dD_rows, dz = _C.ssd_ygate_bwd(
+                dout.contiguous(), ydiag, yoff, dacs, x2d, D_f, z2d, H, G, P,
+                Q)
         dD = dD_rows.sum(0)
         return (dydiag, dyoff, ddacs, dx, dD.to(ddt), dz, None, None, None,
-                None)
+                None, None)
 
 
-def ssd_ygate(ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q):
+def ssd_ygate(ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q, doc_mask=None):
     """ydiag h-major (b,nc,h,Q,p) flat; yoff in the y_off einsum's
     natural (b,nc,g,Q,rep,p) layout; out (b, l, H*P) row-major."""
-    return _SSDYGateFn.apply(ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q)
+    if not x2d.is_cuda:
+        return reference.ssd_ygate(ydiag, yoff, dacs, x2d, D, z2d, H, G, P,
+                                   Q, doc_mask)
+    return _SSDYGateFn.apply(ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q,
+                             *_doc_start_arg(doc_mask, x2d.shape[0], Q))
 
 
 # --------------------------------------------------------------------------

@@ -65,10 +65,10 @@ int attn_sched_mode(int);
 int attn_dkv_mode(int);
 long long attn_bwd_ws_limit(long long);
 void launch_cconv_fwd(const void*, const void*, const float*, void*, int,
-                      int, int, int, hipStream_t);
+                      int, int, int, const int*, hipStream_t);
 void launch_cconv_bwd(const void*, const void*, const void*, const float*,
                       void*, void*, float*, float*, int, int, int, int,
-                      hipStream_t);
+                      const int*, const int*, hipStream_t);
 int launch_gemm_nt(const void*, const void*, void*, int, int, int,
                    hipStream_t);
 void launch_segsum_exp_fwd(const float*, void*, long long, int, hipStream_t);
@@ -81,22 +81,26 @@ void launch_ssd_prep_bwd(const float*, const float*, const void*,
                          long long, int, int, long long, long long,
                          hipStream_t);
 void launch_ssd_xdt_fwd(const void*, const float*, const float*, void*, void*,
-                        long long, int, int, int, long long, hipStream_t);
+                        long long, int, int, int, long long, const int*, int,
+                        hipStream_t);
 void launch_ssd_xdt_bwd(const void*, const void*, const void*, const float*,
                         const float*, void*, float*, float*, long long, int,
-                        int, int, long long, long long, hipStream_t);
+                        int, int, long long, long long, const int*, int,
+                        hipStream_t);
 void launch_ssd_sl_fwd(const float*, const void*, void*, long long, int, int,
-                       int, hipStream_t);
+                       int, const int*, int, hipStream_t);
 void launch_ssd_sl_bwd(const void*, const void*, const float*, void*, float*,
-                       long long, int, int, int, hipStream_t);
+                       long long, int, int, int, const int*, int,
+                       hipStream_t);
 void launch_ssd_ygate_fwd(const void*, const void*, const float*, const void*,
                           const float*, const void*, void*, long long, int,
-                          int, int, int, long long, long long, hipStream_t);
+                          int, int, int, long long, long long, const int*,
+                          int, hipStream_t);
 void launch_ssd_ygate_bwd(const void*, const void*, const void*, const float*,
                           const void*, const float*, const void*, void*,
                           void*, float*, void*, float*, void*, long long, int,
                           int, int, int, long long, long long, long long,
-                          long long, hipStream_t);
+                          long long, const int*, int, hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -774,26 +778,64 @@ std::tuple<Tensor, Tensor, Tensor> attn_bwd_doc(
   return {dq, dk.to(torch::kBFloat16), dv.to(torch::kBFloat16)};
 }
 
-Tensor cconv_fwd(Tensor x, Tensor w, Tensor bias) {
+// Flat document array of the masked SSD / conv entry points (a DocMask's
+// start or end, (b, l) int32): one element per token row of `like`, on
+// its device. Returns the pointer, or nullptr when no mask was given.
+// Runs with the other argument checks, before any launch.
+static const int* doc_ptr(const c10::optional<Tensor>& t, long long rows,
+                          const Tensor& like, const char* nm) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->scalar_type() == torch::kInt32, nm, " must be int32");
+  TORCH_CHECK(t->is_contiguous(), nm, " must be contiguous");
+  TORCH_CHECK(t->device() == like.device(), nm,
+              " must be on the device of the activations");
+  TORCH_CHECK(t->numel() == rows, nm, " must have b*l elements");
+  return t->data_ptr<int>();
+}
+
+// chunks per row of the masked SSD kernels: l a multiple of Q, rows of l
+static int doc_nc(long long rows, int64_t l, int64_t Q) {
+  TORCH_CHECK(l > 0 && l % Q == 0 && rows % l == 0,
+              "row length l must be a multiple of Q and divide the rows");
+  TORCH_CHECK(l < (1LL << 31) && rows / Q < (1LL << 31),
+              "masked SSD kernels index chunks and row positions in 32 bits");
+  return (int)(l / Q);
+}
+
+static Tensor cconv_fwd_impl(Tensor x, Tensor w, Tensor bias,
+                             c10::optional<Tensor> doc_start) {
   CHECK_BF16_CONTIG(x);
   CHECK_BF16_CONTIG(w);
   const int b = x.size(0), l = x.size(1), c = x.size(2);
   const int W = w.size(1);
   TORCH_CHECK(c % 8 == 0 && W >= 2 && W <= 4);
   TORCH_CHECK(bias.scalar_type() == torch::kFloat32);
+  const int* ds = doc_ptr(doc_start, (long long)b * l, x, "doc_start");
   auto y = torch::empty_like(x);
   launch_cconv_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr<float>(),
-                   y.data_ptr(), b * l, l, c, W, cur_stream());
+                   y.data_ptr(), b * l, l, c, W, ds, cur_stream());
   return y;
 }
 
-std::tuple<Tensor, Tensor, Tensor> cconv_bwd(Tensor dy, Tensor x, Tensor w,
-                                             Tensor bias) {
+Tensor cconv_fwd(Tensor x, Tensor w, Tensor bias) {
+  return cconv_fwd_impl(x, w, bias, c10::nullopt);
+}
+
+// Document-masked conv: tap x[r] of output t counts iff r >= doc_start[t].
+Tensor cconv_fwd_doc(Tensor x, Tensor w, Tensor bias, Tensor doc_start) {
+  return cconv_fwd_impl(x, w, bias, doc_start);
+}
+
+static std::tuple<Tensor, Tensor, Tensor> cconv_bwd_impl(
+    Tensor dy, Tensor x, Tensor w, Tensor bias,
+    c10::optional<Tensor> doc_start, c10::optional<Tensor> doc_end) {
   CHECK_BF16_CONTIG(dy);
   CHECK_BF16_CONTIG(x);
   const int b = x.size(0), l = x.size(1), c = x.size(2);
   const int W = w.size(1);
   TORCH_CHECK(c % 8 == 0 && W >= 2 && W <= 4);
+  const int* ds = doc_ptr(doc_start, (long long)b * l, x, "doc_start");
+  const int* de = doc_ptr(doc_end, (long long)b * l, x, "doc_end");
   auto g = torch::empty_like(x);
   auto dx = torch::empty_like(x);
   auto dw = torch::zeros({c, W}, x.options().dtype(torch::kFloat32));
@@ -801,8 +843,21 @@ std::tuple<Tensor, Tensor, Tensor> cconv_bwd(Tensor dy, Tensor x, Tensor w,
   launch_cconv_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
                    bias.data_ptr<float>(), g.data_ptr(), dx.data_ptr(),
                    dw.data_ptr<float>(), db.data_ptr<float>(), b * l, l, c, W,
-                   cur_stream());
+                   ds, de, cur_stream());
   return {dx, dw, db};
+}
+
+std::tuple<Tensor, Tensor, Tensor> cconv_bwd(Tensor dy, Tensor x, Tensor w,
+                                             Tensor bias) {
+  return cconv_bwd_impl(dy, x, w, bias, c10::nullopt, c10::nullopt);
+}
+
+// Backward of cconv_fwd_doc; doc_end[t] = start of the document after t's.
+std::tuple<Tensor, Tensor, Tensor> cconv_bwd_doc(Tensor dy, Tensor x,
+                                                 Tensor w, Tensor bias,
+                                                 Tensor doc_start,
+                                                 Tensor doc_end) {
+  return cconv_bwd_impl(dy, x, w, bias, doc_start, doc_end);
 }
 
 Tensor segsum_exp_fwd(Tensor cs) {
@@ -932,30 +987,49 @@ std::tuple<Tensor, Tensor, Tensor> ssd_prep_bwd(Tensor ddtf, Tensor ddacs,
   return {ddt, dbias, dalog};
 }
 
-std::tuple<Tensor, Tensor> ssd_xdt_fwd(Tensor x, Tensor dtf, Tensor dacs,
-                                       int64_t H, int64_t P, int64_t Q) {
+// The masked (`_doc`) siblings of the xdt / sl / ygate entry points take
+// the flat document starts and the row length l behind the unmasked
+// arguments; see "Document mask" in docs/kernels.md for what each masks.
+static std::tuple<Tensor, Tensor> ssd_xdt_fwd_impl(
+    Tensor x, Tensor dtf, Tensor dacs, int64_t H, int64_t P, int64_t Q,
+    c10::optional<Tensor> doc_start, int64_t l) {
   const long long sx = check_xslice(x, H, P, Q, "x");
   const long long rows = x.size(0);
   check_nq(dtf, rows / Q * H, Q, "dtf");
   check_nq(dacs, rows / Q * H, Q, "dacs");
+  const int* ds = doc_ptr(doc_start, rows, x, "doc_start");
+  const int nc = ds ? doc_nc(rows, l, Q) : 1;
   auto xdt = torch::empty({rows, H * P},
                           x.options().dtype(torch::kBFloat16));
   auto xdtd = torch::empty_like(xdt);
   const long long total8 = rows * H * P / 8;
   launch_ssd_xdt_fwd(x.data_ptr(), dtf.data_ptr<float>(),
                      dacs.data_ptr<float>(), xdt.data_ptr(), xdtd.data_ptr(),
-                     total8, (int)H, (int)Q, (int)P, sx, cur_stream());
+                     total8, (int)H, (int)Q, (int)P, sx, ds, nc,
+                     cur_stream());
   return {xdt, xdtd};
 }
 
-std::tuple<Tensor, Tensor, Tensor> ssd_xdt_bwd(Tensor dxdt, Tensor dxdtd,
-                                               Tensor x, Tensor dtf,
-                                               Tensor dacs, int64_t H,
-                                               int64_t P, int64_t Q) {
+std::tuple<Tensor, Tensor> ssd_xdt_fwd(Tensor x, Tensor dtf, Tensor dacs,
+                                       int64_t H, int64_t P, int64_t Q) {
+  return ssd_xdt_fwd_impl(x, dtf, dacs, H, P, Q, c10::nullopt, 0);
+}
+
+std::tuple<Tensor, Tensor> ssd_xdt_fwd_doc(Tensor x, Tensor dtf, Tensor dacs,
+                                           int64_t H, int64_t P, int64_t Q,
+                                           Tensor doc_start, int64_t l) {
+  return ssd_xdt_fwd_impl(x, dtf, dacs, H, P, Q, doc_start, l);
+}
+
+static std::tuple<Tensor, Tensor, Tensor> ssd_xdt_bwd_impl(
+    Tensor dxdt, Tensor dxdtd, Tensor x, Tensor dtf, Tensor dacs, int64_t H,
+    int64_t P, int64_t Q, c10::optional<Tensor> doc_start, int64_t l) {
   const long long sx = check_xslice(x, H, P, Q, "x");
   const long long rows = x.size(0);
   check_nq(dtf, rows / Q * H, Q, "dtf");
   check_nq(dacs, rows / Q * H, Q, "dacs");
+  const int* ds = doc_ptr(doc_start, rows, x, "doc_start");
+  const int nc = ds ? doc_nc(rows, l, Q) : 1;
   check_bf16_numel(dxdt, rows * H * P, "dxdt");
   check_bf16_numel(dxdtd, rows * H * P, "dxdtd");
   auto dx = torch::empty({rows, H * P}, x.options().dtype(torch::kBFloat16));
@@ -965,8 +1039,22 @@ std::tuple<Tensor, Tensor, Tensor> ssd_xdt_bwd(Tensor dxdt, Tensor dxdtd,
                      dtf.data_ptr<float>(), dacs.data_ptr<float>(),
                      dx.data_ptr(), ddtf.data_ptr<float>(),
                      sdec.data_ptr<float>(), rows * H, (int)H, (int)Q,
-                     (int)P, sx, H * P, cur_stream());
+                     (int)P, sx, H * P, ds, nc, cur_stream());
   return {dx, ddtf, sdec};
+}
+
+std::tuple<Tensor, Tensor, Tensor> ssd_xdt_bwd(Tensor dxdt, Tensor dxdtd,
+                                               Tensor x, Tensor dtf,
+                                               Tensor dacs, int64_t H,
+                                               int64_t P, int64_t Q) {
+  return ssd_xdt_bwd_impl(dxdt, dxdtd, x, dtf, dacs, H, P, Q, c10::nullopt,
+                          0);
+}
+
+std::tuple<Tensor, Tensor, Tensor> ssd_xdt_bwd_doc(
+    Tensor dxdt, Tensor dxdtd, Tensor x, Tensor dtf, Tensor dacs, int64_t H,
+    int64_t P, int64_t Q, Tensor doc_start, int64_t l) {
+  return ssd_xdt_bwd_impl(dxdt, dxdtd, x, dtf, dacs, H, P, Q, doc_start, l);
 }
 
 // dacs (N, Q) fp32 and per-group scores (N/H*G, Q, Q) bf16; returns Q
@@ -987,28 +1075,55 @@ static int check_sl(const Tensor& dacs, const Tensor& scores, int64_t H,
   return (int)Q;
 }
 
-Tensor ssd_sl_fwd(Tensor dacs, Tensor scores, int64_t H, int64_t G) {
+static Tensor ssd_sl_fwd_impl(Tensor dacs, Tensor scores, int64_t H,
+                              int64_t G, c10::optional<Tensor> doc_start,
+                              int64_t l) {
   const int Q = check_sl(dacs, scores, H, G);
   const long long N = dacs.size(0);
+  const int* ds = doc_ptr(doc_start, N / H * Q, dacs, "doc_start");
+  const int nc = ds ? doc_nc(N / H * Q, l, Q) : 1;
   auto out = torch::empty({N, (long long)Q, (long long)Q},
                           scores.options());
   launch_ssd_sl_fwd(dacs.data_ptr<float>(), scores.data_ptr(),
-                    out.data_ptr(), N * Q * (Q / 8), (int)H, (int)G, Q,
-                    cur_stream());
+                    out.data_ptr(), N * Q * (Q / 8), (int)H, (int)G, Q, ds,
+                    nc, cur_stream());
   return out;
 }
 
-std::tuple<Tensor, Tensor> ssd_sl_bwd(Tensor g, Tensor scores, Tensor dacs,
-                                      int64_t H, int64_t G) {
+Tensor ssd_sl_fwd(Tensor dacs, Tensor scores, int64_t H, int64_t G) {
+  return ssd_sl_fwd_impl(dacs, scores, H, G, c10::nullopt, 0);
+}
+
+Tensor ssd_sl_fwd_doc(Tensor dacs, Tensor scores, int64_t H, int64_t G,
+                      Tensor doc_start, int64_t l) {
+  return ssd_sl_fwd_impl(dacs, scores, H, G, doc_start, l);
+}
+
+static std::tuple<Tensor, Tensor> ssd_sl_bwd_impl(
+    Tensor g, Tensor scores, Tensor dacs, int64_t H, int64_t G,
+    c10::optional<Tensor> doc_start, int64_t l) {
   const int Q = check_sl(dacs, scores, H, G);
   const long long N = dacs.size(0);
   check_bf16_numel(g, N * Q * Q, "g");
+  const int* ds = doc_ptr(doc_start, N / H * Q, dacs, "doc_start");
+  const int nc = ds ? doc_nc(N / H * Q, l, Q) : 1;
   auto dsh = torch::empty({N, (long long)Q, (long long)Q}, g.options());
   auto dcs = torch::zeros_like(dacs);
   launch_ssd_sl_bwd(g.data_ptr(), scores.data_ptr(), dacs.data_ptr<float>(),
                     dsh.data_ptr(), dcs.data_ptr<float>(), N, (int)H, (int)G,
-                    Q, cur_stream());
+                    Q, ds, nc, cur_stream());
   return {dsh, dcs};
+}
+
+std::tuple<Tensor, Tensor> ssd_sl_bwd(Tensor g, Tensor scores, Tensor dacs,
+                                      int64_t H, int64_t G) {
+  return ssd_sl_bwd_impl(g, scores, dacs, H, G, c10::nullopt, 0);
+}
+
+std::tuple<Tensor, Tensor> ssd_sl_bwd_doc(Tensor g, Tensor scores,
+                                          Tensor dacs, int64_t H, int64_t G,
+                                          Tensor doc_start, int64_t l) {
+  return ssd_sl_bwd_impl(g, scores, dacs, H, G, doc_start, l);
 }
 
 static void check_ygate(const Tensor& ydiag, const Tensor& yoff,
@@ -1022,31 +1137,50 @@ static void check_ygate(const Tensor& ydiag, const Tensor& yoff,
   check_head_vec(Dp, H, "D");
 }
 
-Tensor ssd_ygate_fwd(Tensor ydiag, Tensor yoff, Tensor dacs, Tensor x,
-                     Tensor Dp, Tensor z, int64_t H, int64_t G, int64_t P,
-                     int64_t Q) {
+static Tensor ssd_ygate_fwd_impl(Tensor ydiag, Tensor yoff, Tensor dacs,
+                                 Tensor x, Tensor Dp, Tensor z, int64_t H,
+                                 int64_t G, int64_t P, int64_t Q,
+                                 c10::optional<Tensor> doc_start, int64_t l) {
   const long long sx = check_xslice(x, H, P, Q, "x");
   const long long sz = check_xslice(z, H, P, Q, "z");
   const long long rows = x.size(0);
   check_ygate(ydiag, yoff, dacs, x, Dp, z, H, G, Q);
+  const int* ds = doc_ptr(doc_start, rows, x, "doc_start");
+  const int nc = ds ? doc_nc(rows, l, Q) : 1;
   auto out = torch::empty({rows, H * P}, x.options().dtype(torch::kBFloat16));
   launch_ssd_ygate_fwd(ydiag.data_ptr(), yoff.data_ptr(),
                        dacs.data_ptr<float>(), x.data_ptr(),
                        Dp.data_ptr<float>(), z.data_ptr(), out.data_ptr(),
                        rows * H * P / 8, (int)H, (int)G, (int)Q, (int)P, sx,
-                       sz, cur_stream());
+                       sz, ds, nc, cur_stream());
   return out;
 }
 
-std::vector<Tensor> ssd_ygate_bwd(Tensor dout, Tensor ydiag, Tensor yoff,
-                                  Tensor dacs, Tensor x, Tensor Dp, Tensor z,
-                                  int64_t H, int64_t G, int64_t P,
-                                  int64_t Q) {
+Tensor ssd_ygate_fwd(Tensor ydiag, Tensor yoff, Tensor dacs, Tensor x,
+                     Tensor Dp, Tensor z, int64_t H, int64_t G, int64_t P,
+                     int64_t Q) {
+  return ssd_ygate_fwd_impl(ydiag, yoff, dacs, x, Dp, z, H, G, P, Q,
+                            c10::nullopt, 0);
+}
+
+Tensor ssd_ygate_fwd_doc(Tensor ydiag, Tensor yoff, Tensor dacs, Tensor x,
+                         Tensor Dp, Tensor z, int64_t H, int64_t G,
+                         int64_t P, int64_t Q, Tensor doc_start, int64_t l) {
+  return ssd_ygate_fwd_impl(ydiag, yoff, dacs, x, Dp, z, H, G, P, Q,
+                            doc_start, l);
+}
+
+static std::vector<Tensor> ssd_ygate_bwd_impl(
+    Tensor dout, Tensor ydiag, Tensor yoff, Tensor dacs, Tensor x, Tensor Dp,
+    Tensor z, int64_t H, int64_t G, int64_t P, int64_t Q,
+    c10::optional<Tensor> doc_start, int64_t l) {
   const long long sx = check_xslice(x, H, P, Q, "x");
   const long long sz = check_xslice(z, H, P, Q, "z");
   const long long rows = x.size(0);
   check_ygate(ydiag, yoff, dacs, x, Dp, z, H, G, Q);
   check_bf16_numel(dout, rows * H * P, "dout");
+  const int* ds = doc_ptr(doc_start, rows, x, "doc_start");
+  const int nc = ds ? doc_nc(rows, l, Q) : 1;
   auto o = x.options().dtype(torch::kBFloat16);
   auto dydiag = torch::empty({rows, H * P}, o);
   auto dyoff = torch::empty({rows, H * P}, o);
@@ -1060,8 +1194,25 @@ std::vector<Tensor> ssd_ygate_bwd(Tensor dout, Tensor ydiag, Tensor yoff,
                        dyoff.data_ptr(), ddacs.data_ptr<float>(),
                        dx.data_ptr(), dD_rows.data_ptr<float>(),
                        dz.data_ptr(), rows * H, (int)H, (int)G, (int)Q,
-                       (int)P, sx, sz, H * P, H * P, cur_stream());
+                       (int)P, sx, sz, H * P, H * P, ds, nc, cur_stream());
   return {dydiag, dyoff, ddacs, dx, dD_rows, dz};
+}
+
+std::vector<Tensor> ssd_ygate_bwd(Tensor dout, Tensor ydiag, Tensor yoff,
+                                  Tensor dacs, Tensor x, Tensor Dp, Tensor z,
+                                  int64_t H, int64_t G, int64_t P,
+                                  int64_t Q) {
+  return ssd_ygate_bwd_impl(dout, ydiag, yoff, dacs, x, Dp, z, H, G, P, Q,
+                            c10::nullopt, 0);
+}
+
+std::vector<Tensor> ssd_ygate_bwd_doc(Tensor dout, Tensor ydiag, Tensor yoff,
+                                      Tensor dacs, Tensor x, Tensor Dp,
+                                      Tensor z, int64_t H, int64_t G,
+                                      int64_t P, int64_t Q, Tensor doc_start,
+                                      int64_t l) {
+  return ssd_ygate_bwd_impl(dout, ydiag, yoff, dacs, x, Dp, z, H, G, P, Q,
+                            doc_start, l);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -1069,6 +1220,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("segsum_exp_bwd", &segsum_exp_bwd);
   mod.def("cconv_fwd", &cconv_fwd);
   mod.def("cconv_bwd", &cconv_bwd);
+  mod.def("cconv_fwd_doc", &cconv_fwd_doc);
+  mod.def("cconv_bwd_doc", &cconv_bwd_doc);
   mod.def("rmsnorm_fwd", &rmsnorm_fwd);
   mod.def("rmsnorm_bwd", &rmsnorm_bwd);
   mod.def("rmsnorm_bwd_into", &rmsnorm_bwd_into);
@@ -1095,6 +1248,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ssd_sl_bwd", &ssd_sl_bwd);
   mod.def("ssd_ygate_fwd", &ssd_ygate_fwd);
   mod.def("ssd_ygate_bwd", &ssd_ygate_bwd);
+  mod.def("ssd_xdt_fwd_doc", &ssd_xdt_fwd_doc);
+  mod.def("ssd_xdt_bwd_doc", &ssd_xdt_bwd_doc);
+  mod.def("ssd_sl_fwd_doc", &ssd_sl_fwd_doc);
+  mod.def("ssd_sl_bwd_doc", &ssd_sl_bwd_doc);
+  mod.def("ssd_ygate_fwd_doc", &ssd_ygate_fwd_doc);
+  mod.def("ssd_ygate_bwd_doc", &ssd_ygate_bwd_doc);
   mod.def("attn_fwd", &attn_fwd);
   mod.def("attn_bwd", &attn_bwd);
   mod.def("kv_append", &kv_append, pybind11::arg("q"), pybind11::arg("k"),

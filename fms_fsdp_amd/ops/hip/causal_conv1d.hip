@@ -10,6 +10,16 @@
 // W times and re-unpacked the weights per output; it measured ~1.9 TB/s
 // effective (230-300 us per call, 12% of the mamba step across the four
 // kernels).
+//
+// DOCMASK instantiations (packed rows, docs/kernels.md "Document mask"):
+// tap x[r] of output t counts iff r >= start[t], the first position of
+// t's document (unmasked: r >= 0). `dstart` / `dend` are the flat (b*L)
+// int32 arrays of ops.DocMask. The strip kernels keep their ring
+// buffers; the mask is a select to 0 where a tap is consumed, with row
+// t's bound read once into a register and clamped (start into [0, t],
+// end into [t+1, L]), so no array content moves an address or a loop
+// bound. A masked tap adds +0 in the same order as an out-of-row tap, so
+// the result equals the unmasked kernel run on the document's slice.
 #include "common.h"
 
 // per-thread 8-channel weight block: channels c0..c0+7, W taps each,
@@ -54,12 +64,13 @@ __device__ __forceinline__ void load_row8(const short* p, float o[8]) {
   const int ts = (int)(r_ % LS) * 8;                                       \
   const long long b_ = r_ / LS;
 
-template <int W>
+template <int W, bool DOCMASK>
 __global__ void cconv_fwd_kernel(const short* __restrict__ x,
                                  const short* __restrict__ w,
                                  const float* __restrict__ bias,
                                  short* __restrict__ y,
-                                 int L, int C, long long nstrip) {
+                                 int L, int C, long long nstrip,
+                                 const int* __restrict__ dstart) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nstrip) return;
   STRIP_DECODE();
@@ -89,13 +100,18 @@ __global__ void cconv_fwd_kernel(const short* __restrict__ x,
     const int t = ts + tt;
     if (t >= L) break;
     load_row8(xb + (long long)t * C, ring[(tt + W - 1) % W]);
+    int st = 0;
+    if (DOCMASK) st = min(max(dstart[b_ * L + t], 0), t);
     bf16x8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float acc = bb[j];
 #pragma unroll
-      for (int wi = 0; wi < W; ++wi)   // row t-(W-1)+wi = slot (tt+wi)%W
-        acc += wf[j][wi] * ring[(tt + wi) % W][j];
+      for (int wi = 0; wi < W; ++wi) { // row t-(W-1)+wi = slot (tt+wi)%W
+        const float xv = (!DOCMASK || t - (W - 1) + wi >= st)
+                             ? ring[(tt + wi) % W][j] : 0.f;
+        acc += wf[j][wi] * xv;
+      }
       const float s = 1.f / (1.f + __expf(-acc));
       o.v[j] = f2bf(acc * s);
     }
@@ -104,13 +120,14 @@ __global__ void cconv_fwd_kernel(const short* __restrict__ x,
 }
 
 // pass 1: g[t,c] = dy[t,c] * dsilu(z[t,c]) with z recomputed
-template <int W>
+template <int W, bool DOCMASK>
 __global__ void cconv_bwd_g_kernel(const short* __restrict__ dy,
                                    const short* __restrict__ x,
                                    const short* __restrict__ w,
                                    const float* __restrict__ bias,
                                    short* __restrict__ g,
-                                   int L, int C, long long nstrip) {
+                                   int L, int C, long long nstrip,
+                                   const int* __restrict__ dstart) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nstrip) return;
   STRIP_DECODE();
@@ -140,13 +157,18 @@ __global__ void cconv_bwd_g_kernel(const short* __restrict__ dy,
     if (t >= L) break;
     load_row8(xb + (long long)t * C, ring[(tt + W - 1) % W]);
     const bf16x8 d = *(const bf16x8*)(dyb + (long long)t * C);
+    int st = 0;
+    if (DOCMASK) st = min(max(dstart[b_ * L + t], 0), t);
     bf16x8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float z = bb[j];
 #pragma unroll
-      for (int wi = 0; wi < W; ++wi)
-        z += wf[j][wi] * ring[(tt + wi) % W][j];
+      for (int wi = 0; wi < W; ++wi) {
+        const float xv = (!DOCMASK || t - (W - 1) + wi >= st)
+                             ? ring[(tt + wi) % W][j] : 0.f;
+        z += wf[j][wi] * xv;
+      }
       const float s = 1.f / (1.f + __expf(-z));
       o.v[j] = f2bf(bf2f(d.v[j]) * s * (1.f + z * (1.f - s)));
     }
@@ -156,11 +178,13 @@ __global__ void cconv_bwd_g_kernel(const short* __restrict__ dy,
 
 // pass 2: dx[t,c] = sum_wi g[t + (W-1) - wi, c] * w[c, wi]
 // (future-looking window: rows t..t+W-1, slot of row r = (r - ts) % W)
-template <int W>
+// DOCMASK: row r counts iff r < end[t], the start of the next document.
+template <int W, bool DOCMASK>
 __global__ void cconv_bwd_dx_kernel(const short* __restrict__ g,
                                     const short* __restrict__ w,
                                     short* __restrict__ dx,
-                                    int L, int C, long long nstrip) {
+                                    int L, int C, long long nstrip,
+                                    const int* __restrict__ dend) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nstrip) return;
   STRIP_DECODE();
@@ -188,13 +212,18 @@ __global__ void cconv_bwd_dx_kernel(const short* __restrict__ g,
     else
 #pragma unroll
       for (int j = 0; j < 8; ++j) ring[(tt + W - 1) % W][j] = 0.f;
+    int en = L;
+    if (DOCMASK) en = min(max(dend[b_ * L + t], t + 1), L);
     bf16x8 o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float acc = 0.f;
 #pragma unroll
-      for (int wi = 0; wi < W; ++wi)   // row t+W-1-wi = slot (tt+W-1-wi)%W
-        acc += wf[j][wi] * ring[(tt + W - 1 - wi) % W][j];
+      for (int wi = 0; wi < W; ++wi) { // row t+W-1-wi = slot (tt+W-1-wi)%W
+        const float gv = (!DOCMASK || t + W - 1 - wi < en)
+                             ? ring[(tt + W - 1 - wi) % W][j] : 0.f;
+        acc += wf[j][wi] * gv;
+      }
       o.v[j] = f2bf(acc);
     }
     *(bf16x8*)(dxb + (long long)t * C) = o;
@@ -203,13 +232,15 @@ __global__ void cconv_bwd_dx_kernel(const short* __restrict__ g,
 
 // pass 3: dw[c,wi] += sum_{b,t} g[t,c] x[t-W+1+wi,c]; db[c] += sum g
 // 8-channel vector loads with the same sliding x window.
-template <int W>
+// DOCMASK: tap row ti counts iff ti >= start[t]; db is unchanged.
+template <int W, bool DOCMASK>
 __global__ void cconv_bwd_dwdb_kernel(const short* __restrict__ g,
                                       const short* __restrict__ x,
                                       float* __restrict__ dw,
                                       float* __restrict__ db,
                                       int L, int C,
-                                      long long rows, int rows_per_chunk) {
+                                      long long rows, int rows_per_chunk,
+                                      const int* __restrict__ dstart) {
   const int c0 = (blockIdx.x * blockDim.x + threadIdx.x) * 8;
   if (c0 >= C) return;
   const long long r0 = (long long)blockIdx.y * rows_per_chunk;
@@ -245,11 +276,13 @@ __global__ void cconv_bwd_dwdb_kernel(const short* __restrict__ g,
     load_row8(g + bt * C + c0, gv);
 #pragma unroll
     for (int j = 0; j < 8; ++j) accb[j] += gv[j];
+    int st = 0;
+    if (DOCMASK) st = min(max(dstart[bt], 0), t);
 #pragma unroll
     for (int wi = 0; wi < W; ++wi) {
       const int ti = t - (W - 1) + wi;
       const int slot = ((ti % W) + W) % W;
-      if (ti >= 0)
+      if (ti >= st)
 #pragma unroll
         for (int j = 0; j < 8; ++j) accw[wi][j] += gv[j] * ring[slot][j];
     }
@@ -265,55 +298,62 @@ __global__ void cconv_bwd_dwdb_kernel(const short* __restrict__ g,
 
 extern "C" {
 
+// dstart / dend (flat (b*L) int32, ops.DocMask) select the DOCMASK
+// instantiations; nullptr is the unmasked kernel.
 void launch_cconv_fwd(const void* x, const void* w, const float* bias,
                       void* y, int BL, int L, int C, int W,
-                      hipStream_t stream) {
+                      const int* dstart, hipStream_t stream) {
   const int B = BL / L;
   const long long nstrip = (long long)B * ((L + 7) / 8) * (C / 8);
   const int block = 256;
   const int grid = (int)((nstrip + block - 1) / block);
-  if (W == 4)
-    cconv_fwd_kernel<4><<<grid, block, 0, stream>>>(
-        (const short*)x, (const short*)w, bias, (short*)y, L, C, nstrip);
-  else if (W == 3)
-    cconv_fwd_kernel<3><<<grid, block, 0, stream>>>(
-        (const short*)x, (const short*)w, bias, (short*)y, L, C, nstrip);
-  else
-    cconv_fwd_kernel<2><<<grid, block, 0, stream>>>(
-        (const short*)x, (const short*)w, bias, (short*)y, L, C, nstrip);
+#define CCONV_FWD(WV, DM)                                                   \
+  cconv_fwd_kernel<WV, DM><<<grid, block, 0, stream>>>(                     \
+      (const short*)x, (const short*)w, bias, (short*)y, L, C, nstrip,      \
+      dstart)
+  if (dstart) {
+    if (W == 4) CCONV_FWD(4, true);
+    else if (W == 3) CCONV_FWD(3, true);
+    else CCONV_FWD(2, true);
+  } else {
+    if (W == 4) CCONV_FWD(4, false);
+    else if (W == 3) CCONV_FWD(3, false);
+    else CCONV_FWD(2, false);
+  }
+#undef CCONV_FWD
 }
 
 void launch_cconv_bwd(const void* dy, const void* x, const void* w,
                       const float* bias, void* g, void* dx, float* dw,
                       float* db, int BL, int L, int C, int W,
+                      const int* dstart, const int* dend,
                       hipStream_t stream) {
   const int B = BL / L;
   const long long nstrip = (long long)B * ((L + 7) / 8) * (C / 8);
   const int block = 256;
   const int grid = (int)((nstrip + block - 1) / block);
-#define CCONV_BWD(WV)                                                       \
-  do {                                                                      \
-    cconv_bwd_g_kernel<WV><<<grid, block, 0, stream>>>(                     \
-        (const short*)dy, (const short*)x, (const short*)w, bias,           \
-        (short*)g, L, C, nstrip);                                           \
-    cconv_bwd_dx_kernel<WV><<<grid, block, 0, stream>>>(                    \
-        (const short*)g, (const short*)w, (short*)dx, L, C, nstrip);        \
-  } while (0)
-  if (W == 4) CCONV_BWD(4);
-  else if (W == 3) CCONV_BWD(3);
-  else CCONV_BWD(2);
-#undef CCONV_BWD
   const int rpc = max(1, (int)((BL + 63) / 64));
   dim3 g2((C / 8 + 255) / 256, (BL + rpc - 1) / rpc);
-  if (W == 4)
-    cconv_bwd_dwdb_kernel<4><<<g2, 256, 0, stream>>>(
-        (const short*)g, (const short*)x, dw, db, L, C, BL, rpc);
-  else if (W == 3)
-    cconv_bwd_dwdb_kernel<3><<<g2, 256, 0, stream>>>(
-        (const short*)g, (const short*)x, dw, db, L, C, BL, rpc);
-  else
-    cconv_bwd_dwdb_kernel<2><<<g2, 256, 0, stream>>>(
-        (const short*)g, (const short*)x, dw, db, L, C, BL, rpc);
+#define CCONV_BWD(WV, DM)                                                   \
+  do {                                                                      \
+    cconv_bwd_g_kernel<WV, DM><<<grid, block, 0, stream>>>(                 \
+        (const short*)dy, (const short*)x, (const short*)w, bias,           \
+        (short*)g, L, C, nstrip, dstart);                                   \
+    cconv_bwd_dx_kernel<WV, DM><<<grid, block, 0, stream>>>(                \
+        (const short*)g, (const short*)w, (short*)dx, L, C, nstrip, dend);  \
+    cconv_bwd_dwdb_kernel<WV, DM><<<g2, 256, 0, stream>>>(                  \
+        (const short*)g, (const short*)x, dw, db, L, C, BL, rpc, dstart);   \
+  } while (0)
+  if (dstart) {
+    if (W == 4) CCONV_BWD(4, true);
+    else if (W == 3) CCONV_BWD(3, true);
+    else CCONV_BWD(2, true);
+  } else {
+    if (W == 4) CCONV_BWD(4, false);
+    else if (W == 3) CCONV_BWD(3, false);
+    else CCONV_BWD(2, false);
+  }
+#undef CCONV_BWD
 }
 
 }  // extern "C"

@@ -110,14 +110,31 @@ def linear_cross_entropy(x, weight, labels, ignore_index=-100):
                            ignore_index=ignore_index)
 
 
-def causal_conv1d(x, weight, bias):
+def causal_conv1d(x, weight, bias, doc_mask=None):
     """Depthwise causal conv + silu (mamba xBC conv). x (b, l, C),
-    weight (C, W), bias (C)."""
+    weight (C, W), bias (C). Computes in fp32, or in float64 when given
+    float64. doc_mask (ops.DocMask): tap x[r] of output t counts iff
+    r >= start[t], i.e. the conv restarts at every document."""
     b, l, C = x.shape
     W = weight.shape[1]
-    xt = x.transpose(1, 2).float()
-    y = F.conv1d(F.pad(xt, (W - 1, 0)), weight.float().unsqueeze(1),
-                 bias.float(), groups=C)
+    if doc_mask is not None:
+        # by definition the plain conv of every document's slice (the
+        # library conv is not bit-stable across lengths, so nothing else
+        # could equal that exactly). Reads the boundaries on the host: an
+        # oracle and the CPU path, not a hot path.
+        pos = torch.arange(l, device=doc_mask.start.device)
+        rows = []
+        for r in range(b):
+            opens = pos[doc_mask.start[r] == pos].tolist()
+            cuts = sorted(set([0] + opens)) + [l]
+            rows.append(torch.cat(
+                [causal_conv1d(x[r:r + 1, s:e], weight, bias)
+                 for s, e in zip(cuts, cuts[1:])], dim=1))
+        return torch.cat(rows, dim=0)
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    xt = x.transpose(1, 2).to(ct)
+    y = F.conv1d(F.pad(xt, (W - 1, 0)), weight.to(ct).unsqueeze(1),
+                 bias.to(ct), groups=C)
     return F.silu(y).transpose(1, 2).to(x.dtype)
 
 
@@ -126,7 +143,23 @@ def causal_conv1d(x, weight, bias):
 # and group mapping of Mamba2Mixer._scan_fused. They compute in the dtype
 # they are given (float64 in the tests); backward comes from autograd.
 # Row index of the (N, Q) tensors: n = bc*H + h with bc = b*nc + c.
+#
+# doc_mask (ops.DocMask of the (b, l) rows the chunks were cut from)
+# resets the scan at every document start: position i depends on j iff
+# start[i] <= j <= i. Over the chunked algorithm that is three selects to
+# exact 0 (docs/kernels.md "Document mask"), all on the chunk-relative
+# start of a token's document; the fourth, on the inter-chunk matrix,
+# lives with the model (models/mamba.py doc_chunk_keep).
 # --------------------------------------------------------------------------
+def doc_rel_start(doc_mask, Q, device):
+    """(bc, Q) int64: start of each token's document relative to the first
+    position of its chunk; negative = it began in an earlier chunk."""
+    start = doc_mask.start.to(device).long()
+    b, l = start.shape
+    first = torch.arange(l, device=device) // Q * Q
+    return (start - first).reshape(b * (l // Q), Q)
+
+
 def ssd_prep(dt2d, dt_bias, A_log, Q):
     """dt2d (b*l, H) -> dtf, dacs (N, Q): dtf = softplus(dt + bias),
     dacs = chunk-local cumsum of dtf * -exp(A_log)."""
@@ -137,39 +170,56 @@ def ssd_prep(dt2d, dt_bias, A_log, Q):
     return dtf.reshape(-1, Q), dacs.reshape(-1, Q)
 
 
-def ssd_xdt(x2d, dtf, dacs, H, P, Q):
+def ssd_xdt(x2d, dtf, dacs, H, P, Q, doc_mask=None):
     """x2d (b*l, H*P) -> xdt = x*dtf and xdtd = xdt*exp(dacs_end - dacs),
-    both h-major (bc, H, Q, P) flattened to (b*l, H*P)."""
+    both h-major (bc, H, Q, P) flattened to (b*l, H*P). doc_mask: xdtd is
+    0 before the start of the chunk's last document (only that document
+    feeds the state the chunk hands on)."""
     rows = x2d.shape[0]
     bc = rows // Q
     xh = x2d.reshape(bc, Q, H, P).permute(0, 2, 1, 3)        # (bc, H, Q, P)
     cs = dacs.view(bc, H, Q)
     xdt = xh * dtf.view(bc, H, Q, 1)
     xdtd = xdt * torch.exp(cs[..., -1:] - cs).unsqueeze(-1)
+    if doc_mask is not None:
+        rel = doc_rel_start(doc_mask, Q, x2d.device)
+        keep = torch.arange(Q, device=x2d.device) >= rel[:, -1:]   # (bc, Q)
+        xdtd = torch.where(keep.view(bc, 1, Q, 1), xdtd,
+                           torch.zeros_like(xdtd))
     return xdt.reshape(rows, H * P), xdtd.reshape(rows, H * P)
 
 
-def ssd_scores_decay(dacs, scores3d, H, G):
+def ssd_scores_decay(dacs, scores3d, H, G, doc_mask=None):
     """sL[n, i, j] = scores[m, i, j] * exp(dacs[n, i] - dacs[n, j]) for
-    j <= i, else 0; scores per group: m = bc*G + h // (H // G)."""
+    j <= i, else 0; scores per group: m = bc*G + h // (H // G). doc_mask:
+    additionally 0 where j lies before the start of i's document."""
     N, Q = dacs.shape
     rep = H // G
     diff = dacs[:, :, None] - dacs[:, None, :]
     mask = torch.tril(torch.ones(Q, Q, dtype=torch.bool, device=dacs.device))
+    if doc_mask is not None:
+        rel = doc_rel_start(doc_mask, Q, dacs.device)             # (bc, Q)
+        inside = torch.arange(Q, device=dacs.device) >= rel[:, :, None]
+        mask = (mask & inside).repeat_interleave(H, dim=0)        # (N, Q, Q)
     L = torch.exp(diff.masked_fill(~mask, -torch.inf))
     s = scores3d.view(N // H, G, 1, Q, Q).expand(-1, -1, rep, -1, -1)
     return s.reshape(N, Q, Q) * L
 
 
-def ssd_ygate(ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q):
+def ssd_ygate(ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q, doc_mask=None):
     """out = (ydiag + yoff*exp(dacs) + x*D) * silu(z), (b*l, H*P).
-    ydiag h-major (bc, H, Q, P); yoff (bc, G, Q, rep, P)."""
+    ydiag h-major (bc, H, Q, P); yoff (bc, G, Q, rep, P). doc_mask: the
+    yoff term counts only for tokens whose document began before their
+    chunk."""
     rows = x2d.shape[0]
     bc = rows // Q
     rep = H // G
     yd = ydiag.reshape(bc, H, Q, P).permute(0, 2, 1, 3)      # (bc, Q, H, P)
     yo = yoff.reshape(bc, G, Q, rep, P).permute(0, 2, 1, 3, 4) \
         .reshape(bc, Q, H, P)
+    if doc_mask is not None:
+        off = doc_rel_start(doc_mask, Q, x2d.device) < 0          # (bc, Q)
+        yo = torch.where(off.view(bc, Q, 1, 1), yo, torch.zeros_like(yo))
     sd = torch.exp(dacs.view(bc, H, Q)).permute(0, 2, 1).unsqueeze(-1)
     xh = x2d.reshape(bc, Q, H, P)
     zh = z2d.reshape(bc, Q, H, P)

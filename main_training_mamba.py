@@ -47,6 +47,9 @@ def main(**kwargs):
     mcfg = MambaConfig.from_dict(get_model_config(cfg.model_variant))
     model = MambaLMHeadModel(mcfg)
     model.reset_parameters()
+    if cfg.doc_mask:
+        # documents are packed back to back, each ending in eos_token
+        model.doc_mask_token = cfg.eos_token
     if rank == 0:
         print(f"--> mamba model has {model.param_count() / 1e6:.2f}M params")
 
