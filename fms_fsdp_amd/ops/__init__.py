@@ -303,9 +303,28 @@ def rope_apply(q, k, cos, sin):
 # hipBLASLt's default algorithms, wins and losses are mixed. Hence:
 # tokens >= 8192 and a weight of at least 4096 x 8192 elements.
 # FMS_AMD_WGRAD=nt keeps every wgrad on the old route.
+#
+# The dgrad dx = dy @ W finds W strided along the reduction (BLAS "NN"),
+# the second slowest class. _C.dgrad_tn transposes W with transpose.hip
+# into a transient copy right before its GEMM and runs dy @ WT^T, again
+# the forward's class. The copy is made per backward use and freed by
+# stream-ordered reuse: no cache, nothing to invalidate when the
+# optimizer, a gather or a checkpoint load writes the weight. An earlier
+# attempt at this route lost 29 ms/step; it transposed with torch's
+# generic w.t().contiguous() kernel per GEMM, several times slower than
+# transpose.hip. Measured with transpose.hip
+# (profiles/7b_1gpu_step_dgrad_tn.md): at 8192 tokens the whole op
+# (transpose + GEMM) gains 17, 37 and 113 us on qkv, gate|up and down, and
+# loses 5 us on the square 4096 x 4096 projection, whose 67 MB transpose
+# runs at only 2.0 TB/s; at 4096 tokens and below every projection but
+# one loses, the transpose being a fixed cost. Hence the wgrad's rule:
+# tokens >= 8192 and a weight of at least 4096 x 8192 elements.
+# FMS_AMD_DGRAD=nn keeps every dgrad on the old route.
 # --------------------------------------------------------------------------
 _WGRAD_TN_MIN_TOKENS = 8192
 _WGRAD_TN_MIN_WEIGHT = 4096 * 8192   # out * in
+_DGRAD_TN_MIN_TOKENS = 8192
+_DGRAD_TN_MIN_WEIGHT = 4096 * 8192   # out * in
 
 
 def _wgrad_mode(dy2, x2):
@@ -327,6 +346,27 @@ def _wgrad_mode(dy2, x2):
                 or t.data_ptr() % 16):
             return 0
     return 3
+
+
+def _dgrad_mode(dy2, w):
+    """True where the dgrad dx = dy2 @ w goes through _C.dgrad_tn; False =
+    the plain matmul on the operands as they are."""
+    if _C is None or os.environ.get("FMS_AMD_DGRAD") == "nn":
+        return False
+    if not (dy2.is_cuda and w.is_cuda and dy2.dtype == torch.bfloat16
+            and w.dtype == torch.bfloat16 and dy2.dim() == 2 and w.dim() == 2):
+        return False
+    tokens, out = dy2.shape
+    inn = w.shape[1]
+    if out != w.shape[0] or out % 8 or inn % 8:
+        return False
+    if tokens < _DGRAD_TN_MIN_TOKENS or out * inn < _DGRAD_TN_MIN_WEIGHT:
+        return False
+    if dy2.stride(1) != 1 or dy2.stride(0) < out:   # the GEMM reads it as is
+        return False
+    # what transpose.hip reads without a copy
+    return not (w.stride(1) != 1 or w.stride(0) % 8 or w.stride(0) < inn
+                or w.data_ptr() % 16)
 
 
 class _DirectWgradLinearFn(torch.autograd.Function):
@@ -352,12 +392,12 @@ class _DirectWgradLinearFn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         dy2 = dy.reshape(-1, dy.shape[-1])
         x2 = x.reshape(-1, x.shape[-1])
-        # NOTE: rerouting this dgrad through a transposed weight copy
-        # (mm(dy, wT.t()) = hipBLASLt's faster "TN" class instead of the
-        # "NN" class this layout hits) measured 29 ms/step SLOWER on the
-        # 7B bench — the .t().contiguous() sweeps cost more than the
-        # GEMM class difference saves. Measured and rejected.
-        dx = (dy2 @ w).view(x.shape)
+        if not ctx.needs_input_grad[0]:
+            dx = None
+        elif _dgrad_mode(dy2, w):
+            dx = _C.dgrad_tn(dy2, w).view(x.shape)
+        else:
+            dx = (dy2 @ w).view(x.shape)
         # wgrad straight into the flat grad buffer. First touch since
         # zero_grad overwrites (beta=0) so the runtime never has to
         # zero-fill these slices; later touches accumulate (beta=1).

@@ -361,6 +361,38 @@ void wgrad_tn(Tensor dy2, Tensor x2, Tensor gview, bool accumulate,
 // Calls of wgrad_tn so far: lets a test see which route a backward took.
 int64_t wgrad_tn_calls() { return wgrad_tn_count; }
 
+// dx = dy2 @ w for dy2 (tokens, out) and a weight w (out, in). As it
+// stands the product finds w strided along the reduction (BLAS "NN");
+// with w transposed first by transpose.hip it is dy2 @ wT^T, the forward's
+// class ("TN"). dy2 is read in place: unit column stride and a row stride
+// >= out (the fused dqkv buffer and its column slices qualify). The
+// transposed weight comes from the caching allocator and dies with this
+// call (stream-ordered reuse): nothing is cached, so nothing has to be
+// invalidated when the optimizer or the sharded runtime writes w.
+static int64_t dgrad_tn_count = 0;
+
+Tensor dgrad_tn(Tensor dy2, Tensor w) {
+  TORCH_CHECK(dy2.is_cuda() && dy2.scalar_type() == torch::kBFloat16 &&
+                  dy2.dim() == 2 && dy2.size(0) > 0 && dy2.size(1) > 0 &&
+                  dy2.stride(1) == 1 && dy2.stride(0) >= dy2.size(1),
+              "dgrad_tn: dy2 must be a bf16 GPU tensor (tokens, out) with "
+              "unit column stride and a row stride >= out");
+  TORCH_CHECK(transpose_src_ok(w) && w.size(0) % 8 == 0,
+              "dgrad_tn: w must be a bf16 GPU tensor (out, in), out % 8 == 0, "
+              "in % 8 == 0, unit column stride, row stride a multiple of 8 "
+              "and >= in, 16-byte aligned");
+  TORCH_CHECK(dy2.size(1) == w.size(0) && dy2.device() == w.device(),
+              "dgrad_tn: dy2 (tokens, out) and w (out, in) on one device "
+              "expected");
+  Tensor wT = transpose_bf16(w, c10::nullopt);   // (in, out), contiguous
+  Tensor dx = at::mm(dy2, wT.t());
+  ++dgrad_tn_count;
+  return dx;
+}
+
+// Calls of dgrad_tn so far: lets a test see which route a backward took.
+int64_t dgrad_tn_calls() { return dgrad_tn_count; }
+
 void ce_fwd_bwd(Tensor logits, Tensor labels, Tensor loss_sum, Tensor denom,
                 int64_t ignore_index) {
   CHECK_BF16_CONTIG(logits);
@@ -1236,6 +1268,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("out") = pybind11::none());
   mod.def("wgrad_tn", &wgrad_tn);
   mod.def("wgrad_tn_calls", &wgrad_tn_calls);
+  mod.def("dgrad_tn", &dgrad_tn);
+  mod.def("dgrad_tn_calls", &dgrad_tn_calls);
   mod.def("ce_fwd_bwd", &ce_fwd_bwd);
   mod.def("adamw", &adamw);
   mod.def("sq_norm_accum", &sq_norm_accum);

@@ -1,6 +1,7 @@
 // bf16 matrix transpose: dst (cols x rows, contiguous) = src^T, src
 // (rows x cols) with a row stride >= cols. Feeds the wgrad GEMMs their
-// operands token-contiguous (ops/__init__.py, _DirectWgradLinearFn), so
+// operands token-contiguous and the dgrad GEMMs their weight transposed
+// (ops/__init__.py, _DirectWgradLinearFn; _C.wgrad_tn and _C.dgrad_tn), so
 // it has to run near copy speed: every global access is a 16-B access
 // along a row, of the source on the way in and of the destination on the
 // way out, and the 2-byte element shuffle happens in a 64x64 LDS tile.
@@ -26,7 +27,9 @@
 
 // vec_dst: rows % 8 == 0, so every 8-element run of a destination row is
 // 16-B aligned. Otherwise the drain stores element-wise (correct for any
-// rows; the wgrad route never takes it).
+// rows; neither route takes it: the wgrad's rows are the tokens, a
+// multiple of 8 by its rule, the dgrad's are the weight's `out`, which
+// _C.dgrad_tn checks).
 template <bool vec_dst>
 __global__ __launch_bounds__(256) void transpose_bf16_kernel(
     const short* __restrict__ src, short* __restrict__ dst, long long rows,
