@@ -92,7 +92,8 @@ def _doc_rel_start(doc_start, chunk):
     return (doc_start.long() - first).view(b, l // chunk, chunk)
 
 
-def ssd_chunked(x, dt, A, B, C, chunk, doc_start=None):
+def ssd_chunked(x, dt, A, B, C, chunk, doc_start=None,
+                return_final_state=False):
     """State-space dual scan (fp32 math).
 
     x (b,l,h,p), dt (b,l,h) [already softplus'ed], A (h) [negative],
@@ -106,6 +107,10 @@ def ssd_chunked(x, dt, A, B, C, chunk, doc_start=None):
     it), the inter-chunk W (doc_chunk_keep) and the decay out of the
     carried state (only tokens whose document began before their chunk
     read it).
+
+    return_final_state: also return the state after the last token, fp32
+    (b, h, p, n): the row of the inter-chunk matrix the scan itself never
+    needs (the decay of every chunk's state to the end of the sequence).
     """
     b, l, h, p = x.shape
     g, n = B.shape[2], B.shape[3]
@@ -193,7 +198,11 @@ def ssd_chunked(x, dt, A, B, C, chunk, doc_start=None):
         prev_states.view(b, nc, g, rep, n, p).to(mm_dtype)).float() \
         .reshape(b, nc, chunk, h, p)
     y_off = y_off * state_decay.permute(0, 1, 3, 2).unsqueeze(-1)
-    return (y_diag + y_off).reshape(b, l, h, p)
+    y = (y_diag + y_off).reshape(b, l, h, p)
+    if return_final_state:
+        final = torch.einsum("bhc,bchnp->bhnp", W[:, :, -1], states.float())
+        return y, final.permute(0, 1, 3, 2).contiguous()
+    return y
 
 
 class Mamba2Mixer(nn.Module):
@@ -242,7 +251,7 @@ class Mamba2Mixer(nn.Module):
         self.norm.reset_parameters()
 
     def _scan_fused(self, b, l, x, dt, z, B, C, dtb, Alog, D_,
-                    doc_start=None, doc_end=None):
+                    doc_start=None, doc_end=None, return_final_state=False):
         """GPU SSD scan: the elementwise chains run as fused HIP kernels
         (ops/hip/ssd.hip — prep/xdt/scores-decay/ygate, each with a
         custom backward); only the MFMA-shaped work (scores, y_diag,
@@ -252,7 +261,9 @@ class Mamba2Mixer(nn.Module):
         Returns the gated (b, l, d_inner) bf16 activations (pre-norm).
         doc_start/doc_end (a DocMask's arrays) reset the scan at every
         document start: masked xdt / scores-decay / ygate kernels plus a
-        select on the inter-chunk matrix (see ssd_chunked)."""
+        select on the inter-chunk matrix (see ssd_chunked).
+        return_final_state: also the fp32 (b, h, p, n) state after the last
+        token (see ssd_chunked)."""
         doc_mask = None if doc_start is None else ops.DocMask(doc_start,
                                                               doc_end)
         h, p = self.nheads, self.headdim
@@ -304,11 +315,86 @@ class Mamba2Mixer(nn.Module):
             y_diag.reshape(b * l, h * p),
             y_off.contiguous().view(b * l, h * p),
             dacs, x2, D_, z2, h, g, p, Q, doc_mask=doc_mask)
+        if return_final_state:
+            final = torch.einsum("bhc,bchnp->bhnp", W[:, :, -1],
+                                 states.float())
+            return out.view(b, l, h * p), \
+                final.permute(0, 1, 3, 2).contiguous()
         return out.view(b, l, h * p)
 
-    def forward(self, u, doc_mask=None):
+    def _fused_scan_ok(self, u):
+        return u.is_cuda and u.dtype == torch.bfloat16 \
+            and not getattr(self, "_force_torch_scan", False) \
+            and os.environ.get("FMS_AMD_FORCE_TORCH_SCAN") != "1"
+
+    def _forward_cached(self, u, cache):
+        """l new tokens over an ops.MambaCache (inference only). in_proj
+        and the conv run once over all l tokens. On a fresh cache the
+        first l // chunk * chunk tokens take the chunked scan, which hands
+        its final state to the cache; the remaining l % chunk tokens, and
+        every token on a cache already in use (the single decode token as
+        a rule), step the recurrence from the cached state with
+        ops.ssd_state_update."""
+        if torch.is_grad_enabled() and (
+                u.requires_grad or self.in_proj.weight.requires_grad):
+            raise RuntimeError(
+                "the Mamba2 state cache has no backward: call the model "
+                "under torch.no_grad()")
+        b, l, _ = u.shape
+        h, p, g, n = self.nheads, self.headdim, self.ngroups, self.d_state
+        Q = self.chunk
+        fresh = cache.len == 0
+        zxbcdt = ops.linear_flat(u, self.in_proj.weight)
+        z, xBC, dt = torch.split(
+            zxbcdt, [self.d_inner, self.conv_dim, self.nheads], dim=-1)
+        if fresh and l > 1:
+            raw = xBC
+            xBC = ops.causal_conv1d(raw, self.conv_weight, self.conv_bias)
+            # the last W-1 raw rows; a shorter prompt keeps zeros in front
+            k = min(l, self.d_conv - 1)
+            cache.conv[:, self.d_conv - 1 - k:] = raw[:, l - k:]
+        else:
+            xBC = ops.causal_conv1d_update(cache.conv, xBC, self.conv_weight,
+                                           self.conv_bias)
+        x, B, C = torch.split(xBC, [self.d_inner, g * n, g * n], dim=-1)
+
+        outs = []
+        m = l // Q * Q if fresh else 0
+        if m:
+            xm, dtm, zm, Bm, Cm = (t[:, :m] for t in (x, dt, z, B, C))
+            if self._fused_scan_ok(u):
+                y, final = self._scan_fused(
+                    b, m, xm, dtm, zm, Bm, Cm, self.dt_bias, self.A_log,
+                    self.D, return_final_state=True)
+            else:
+                dtf = F.softplus(dtm.float() + self.dt_bias.float())
+                xh = xm.reshape(b, m, h, p).float()
+                y, final = ssd_chunked(
+                    xh, dtf, -torch.exp(self.A_log.float()),
+                    Bm.reshape(b, m, g, n).float(),
+                    Cm.reshape(b, m, g, n).float(), Q,
+                    return_final_state=True)
+                y = y + xh * self.D.view(1, 1, -1, 1)
+                y = y.reshape(b, m, self.d_inner).to(u.dtype) * F.silu(zm)
+            cache.ssm.copy_(final)
+            outs.append(y)
+        if m < l:
+            outs.append(ops.ssd_state_update(
+                cache.ssm, x[:, m:], dt[:, m:], B[:, m:], C[:, m:], z[:, m:],
+                self.dt_bias, self.A_log, self.D, h, g, p, n))
+        cache.len += l
+        y = outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+        return ops.linear_flat(self.norm(y), self.out_proj.weight)
+
+    def forward(self, u, doc_mask=None, cache=None):
         """doc_mask (ops.DocMask): conv and SSM state restart at every
-        document of a packed row."""
+        document of a packed row. cache (ops.MambaCache): the tokens
+        continue the cached sequence (_forward_cached); any length."""
+        if cache is not None:
+            if doc_mask is not None:
+                raise ValueError("a state cache holds one sequence per row: "
+                                 "cache and doc_mask do not combine")
+            return self._forward_cached(u, cache)
         b, l, _ = u.shape
         zxbcdt = ops.linear_flat(u, self.in_proj.weight)
         z, xBC, dt = torch.split(
@@ -393,7 +479,12 @@ class MambaAttnMixer(nn.Module):
         if self.proj.bias is not None:
             nn.init.zeros_(self.proj.bias)
 
-    def forward(self, x, doc_mask=None):
+    def forward(self, x, doc_mask=None, cache=None):
+        """cache (ops.KVCache): the s tokens continue the cached sequence
+        at positions [cache.len, cache.len + s)."""
+        if cache is not None and doc_mask is not None:
+            raise ValueError("a KV cache holds one sequence per row: cache "
+                             "and doc_mask do not combine")
         b, s, _ = x.shape
         qkv = (self.qkv(x) if self.qkv.bias is not None
                else ops.linear_flat(x, self.qkv.weight))
@@ -404,15 +495,22 @@ class MambaAttnMixer(nn.Module):
         k = k.view(b, s, self.kvheads, self.head_dim)
         v = v.view(b, s, self.kvheads, self.head_dim)
         if self.rot_dim:
-            cos, sin = self.rot_emb.get(s, x.device)
+            pos = 0 if cache is None else cache.len
+            cos, sin = self.rot_emb.get(pos + s, x.device)
+            if cache is not None:
+                cos, sin = cos[pos:], sin[pos:]
             qr, kr = ops.rope_apply(q[..., :self.rot_dim].contiguous(),
                                     k[..., :self.rot_dim].contiguous(),
                                     cos, sin)
             q = torch.cat([qr, q[..., self.rot_dim:]], dim=-1)
             k = torch.cat([kr, k[..., self.rot_dim:]], dim=-1)
-        # rotary positions are not reset per document (as in Llama)
-        o = ops.attention_causal(q.contiguous(), k.contiguous(),
-                                 v.contiguous(), doc_mask=doc_mask)
+        if cache is not None:
+            # q and k are rotated already: append only, no tables
+            o = ops.attention_cached(q, k, v, cache)
+        else:
+            # rotary positions are not reset per document (as in Llama)
+            o = ops.attention_causal(q.contiguous(), k.contiguous(),
+                                     v.contiguous(), doc_mask=doc_mask)
         o2 = o.reshape(b, s, -1)
         if self.proj.bias is not None:
             return self.proj(o2)
@@ -462,14 +560,15 @@ class MambaBlock(nn.Module):
             self.norm2.reset_parameters()
             self.mlp.reset_parameters()
 
-    def forward(self, x, doc_mask=None):
-        if getattr(self, "_ac_enabled", False) and torch.is_grad_enabled():
+    def forward(self, x, doc_mask=None, cache=None):
+        if cache is None and getattr(self, "_ac_enabled", False) \
+                and torch.is_grad_enabled():
             return torch.utils.checkpoint.checkpoint(
                 self._forward_impl, x, doc_mask, use_reentrant=False)
-        return self._forward_impl(x, doc_mask)
+        return self._forward_impl(x, doc_mask, cache)
 
-    def _forward_impl(self, x, doc_mask=None):
-        h = self.mixer(self.norm(x), doc_mask=doc_mask)
+    def _forward_impl(self, x, doc_mask=None, cache=None):
+        h = self.mixer(self.norm(x), doc_mask=doc_mask, cache=cache)
         if self.mlp is not None:
             # fused residual-add + norm (the reference's fused_add_norm,
             # config_utils.py:182 there)
@@ -502,21 +601,88 @@ class MambaLMHeadModel(nn.Module):
         for l in self.layers:
             l.reset_parameters()
 
-    def forward(self, tokens, labels=None, doc_mask=None):
+    def forward(self, tokens, labels=None, doc_mask=None, caches=None):
         """doc_mask (ops.DocMask) keeps every layer inside each document
         of a packed row: the causal conv and the SSM state restart at a
         document's first token and the hybrid's attention layers mask
         across documents. With `doc_mask_token` set it is built from
-        `tokens`, once per forward, and shared by all layers."""
-        if doc_mask is None and self.doc_mask_token is not None:
+        `tokens`, once per forward, and shared by all layers.
+
+        caches (allocate_cache()): `tokens` continue the sequence the
+        caches hold, any number of them; inference only. A cached
+        sequence is one document: an explicit doc_mask raises and
+        `doc_mask_token` is not applied."""
+        if caches is not None:
+            if doc_mask is not None:
+                raise ValueError("caches and doc_mask do not combine")
+            if len(caches) != len(self.layers):
+                raise ValueError(f"{len(self.layers)} layers need as many "
+                                 f"caches, got {len(caches)}")
+        elif doc_mask is None and self.doc_mask_token is not None:
             doc_mask = ops.doc_mask_from_tokens(tokens, self.doc_mask_token)
         x = self.embedding(tokens)
-        for layer in self.layers:
-            x = layer(x, doc_mask=doc_mask)
+        if caches is not None:
+            for layer, cache in zip(self.layers, caches):
+                x = layer(x, cache=cache)
+        else:
+            for layer in self.layers:
+                x = layer(x, doc_mask=doc_mask)
         x = self.norm_f(x)
         if labels is not None:
             return ops.linear_cross_entropy(x, self.lm_head.weight, labels)
         return self.lm_head(x)
+
+    def allocate_cache(self, batch, max_len, dtype, device):
+        """One cache per layer for a sequence of up to max_len tokens: an
+        ops.MambaCache (constant size) for a Mamba2 layer, an ops.KVCache
+        of max_len rows for an attention layer."""
+        caches = []
+        for layer in self.layers:
+            mx = layer.mixer
+            if isinstance(mx, MambaAttnMixer):
+                caches.append(ops.KVCache(batch, max_len, mx.kvheads,
+                                          mx.head_dim, dtype, device))
+            else:
+                caches.append(ops.MambaCache(
+                    batch, mx.conv_dim, mx.d_conv, mx.nheads, mx.headdim,
+                    mx.d_state, dtype, device))
+        return caches
+
+    @torch.no_grad()
+    def generate(self, input_ids, max_new_tokens, temperature=1.0,
+                 do_sample=True, include_embeds=False):
+        """Autoregressive generation over the recurrent state (and the KV
+        caches of a hybrid's attention layers): the prompt, of any length,
+        is consumed in one forward, then one token per step at constant
+        memory in the Mamba2 layers. Signature and return values of
+        Llama.generate: tokens (b, s0 + max_new_tokens), with
+        include_embeds also the final-norm hidden state of every
+        generated position (b, max_new_tokens, d_model)."""
+        b, s0 = input_ids.shape
+        caches = None
+        tokens = input_ids
+        embeds = []
+        cur = input_ids
+        for _ in range(max_new_tokens):
+            x = self.embedding(cur)
+            if caches is None:
+                caches = self.allocate_cache(b, s0 + max_new_tokens, x.dtype,
+                                             x.device)
+            for layer, cache in zip(self.layers, caches):
+                x = layer(x, cache=cache)
+            h_last = self.norm_f(x[:, -1:])
+            logits = self.lm_head(h_last)[:, -1]
+            if do_sample:
+                probs = torch.softmax(logits.float() / temperature, dim=-1)
+                nxt = torch.multinomial(probs, 1)
+            else:
+                nxt = logits.argmax(-1, keepdim=True)
+            embeds.append(h_last)
+            tokens = torch.cat([tokens, nxt], dim=1)
+            cur = nxt
+        if include_embeds:
+            return tokens, torch.cat(embeds, dim=1)
+        return tokens
 
     def param_count(self):
         return sum(p.numel() for p in self.parameters())

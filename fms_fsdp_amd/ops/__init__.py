@@ -782,7 +782,14 @@ def attention_cached(q, k, v, cache, cos=None, sin=None):
         return attention_decode(qr, cache)
     n = cache.len
     if was_empty:
-        return attention_causal(qr, cache.k[:, :n], cache.v[:, :n])
+        kc, vc = cache.k[:, :n], cache.v[:, :n]
+        if kc.shape[0] == 1:
+            # a batch of one counts as contiguous whatever its batch
+            # stride, so no copy is made, yet it reports the capacity's
+            # stride, which the kernel's view check refuses: rebuild the
+            # batch dim with the stride of n rows
+            kc, vc = kc[0].unsqueeze(0), vc[0].unsqueeze(0)
+        return attention_causal(qr, kc, vc)
     return reference.attention_cached(qr, cache.k[:, :n], cache.v[:, :n])
 
 
@@ -929,6 +936,93 @@ def causal_conv1d(x, weight, bias, doc_mask=None):
     if x.is_cuda and x.dtype == torch.bfloat16:
         return _CausalConv1dFn.apply(x, weight, bias, *_doc_arrays(doc_mask))
     return reference.causal_conv1d(x, weight, bias, doc_mask)
+
+
+# --------------------------------------------------------------------------
+# Mamba2 recurrent decode: per-layer state cache, conv update and SSD step
+# (causal_conv1d.hip cconv_update_kernel, ssd_step.hip). Inference only.
+# --------------------------------------------------------------------------
+class MambaCache:
+    """Recurrent state of one Mamba2 layer: `conv` (b, d_conv-1, conv_dim),
+    the last d_conv-1 raw conv inputs, oldest first, in the activation
+    dtype; `ssm` (b, nheads, headdim, d_state) fp32 (mamba_ssm's layout);
+    and the host int `len`, the number of tokens consumed. Both start at
+    zero, which is a fresh sequence. The size does not depend on the
+    length; all batch rows advance together.
+
+    fp16 on a GPU is stored in bf16, the type the kernels compute in."""
+
+    def __init__(self, batch, conv_dim, d_conv, nheads, headdim, d_state,
+                 dtype, device):
+        device = torch.device(device)
+        if dtype == torch.float16 and device.type == "cuda":
+            dtype = torch.bfloat16
+        self.conv = torch.zeros(batch, d_conv - 1, conv_dim, dtype=dtype,
+                                device=device)
+        self.ssm = torch.zeros(batch, nheads, headdim, d_state,
+                               dtype=torch.float32, device=device)
+        self.len = 0
+
+
+def _step_view(t):
+    """What the step kernels read without a copy: (b, T, cols) with a unit
+    last stride, one uniform distance between the (b, t) rows (taken from
+    b at T == 1, as in _append_view) and a row stride and base that keep
+    16-byte alignment."""
+    b, T, cols = t.shape
+    rs = t.stride(1) if T > 1 else (t.stride(0) if b > 1 else cols)
+    ok = (t.stride(2) == 1 and rs >= cols
+          and (T == 1 or b == 1 or t.stride(0) == T * rs)
+          and rs % 8 == 0 and t.data_ptr() % 16 == 0)
+    return t if ok else t.contiguous()
+
+
+def causal_conv1d_update(conv_state, x, weight, bias):
+    """T >= 1 new rows x (b, T, C) of the causal conv behind conv_state
+    (b, W-1, C), updated in place: y = silu(conv + bias) over
+    [state | x], and the state ends as the last W-1 rows of [state | x].
+    On the GPU y equals causal_conv1d on the whole sequence bit for bit.
+    No backward (inference only)."""
+    _decode_no_grad(x, weight, bias)
+    if x.shape[1] < 1:
+        raise ValueError("causal_conv1d_update needs at least one row")
+    if x.is_cuda and x.dtype == torch.float16:
+        return causal_conv1d_update(conv_state, x.bfloat16(), weight,
+                                    bias).half()
+    if x.is_cuda and x.dtype == torch.bfloat16:
+        ext = _require_ext("causal_conv1d_update")
+        return ext.cconv_update(conv_state, _step_view(x),
+                                weight.detach().contiguous().bfloat16(),
+                                bias.detach().float().contiguous())
+    return reference.causal_conv1d_update(conv_state, x, weight, bias)
+
+
+def ssd_state_update(state, x, dt, B, C, z, dt_bias, A_log, D, H, G, P, N):
+    """T >= 1 tokens of the SSD recurrence from `state` (b, H, P, N) fp32,
+    updated in place (reference.ssd_state_update has the definition).
+    x/z (b, T, H*P), B/C (b, T, G*N) and dt (b, T, H) may be last-dim
+    slices of the projections; returns the gated out (b, T, H*P).
+    No backward (inference only)."""
+    _decode_no_grad(x, dt, B, C, z, dt_bias, A_log, D)
+    if x.shape[1] < 1:
+        raise ValueError("ssd_state_update needs at least one token")
+    if x.is_cuda and x.dtype == torch.float16:
+        return ssd_state_update(
+            state, x.bfloat16(), dt.bfloat16(), B.bfloat16(), C.bfloat16(),
+            z.bfloat16(), dt_bias, A_log, D, H, G, P, N).half()
+    if x.is_cuda and x.dtype == torch.bfloat16:
+        ext = _require_ext("ssd_state_update")
+        b, T, _ = dt.shape
+        if dt.stride(2) != 1 or (T > 1 and b > 1
+                                 and dt.stride(0) != T * dt.stride(1)):
+            dt = dt.contiguous()
+        return ext.ssd_step(
+            state, _step_view(x), dt, _step_view(B), _step_view(C),
+            _step_view(z), dt_bias.detach().float().contiguous(),
+            A_log.detach().float().contiguous(),
+            D.detach().float().contiguous(), H, G, P, N)
+    return reference.ssd_state_update(state, x, dt, B, C, z, dt_bias, A_log,
+                                      D, H, G, P, N)
 
 
 # --------------------------------------------------------------------------

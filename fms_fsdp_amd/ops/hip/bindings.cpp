@@ -101,6 +101,13 @@ void launch_ssd_ygate_bwd(const void*, const void*, const void*, const float*,
                           void*, float*, void*, float*, void*, long long, int,
                           int, int, int, long long, long long, long long,
                           long long, const int*, int, hipStream_t);
+void launch_cconv_update(void*, const void*, const void*, const float*, void*,
+                         long long, int, int, int, long long, hipStream_t);
+void launch_ssd_step(float*, const void*, const void*, const void*,
+                     const void*, const void*, const float*, const float*,
+                     const float*, void*, long long, int, int, int, int, int,
+                     long long, long long, long long, long long, long long,
+                     hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -1247,7 +1254,152 @@ std::vector<Tensor> ssd_ygate_bwd_doc(Tensor dout, Tensor ydiag, Tensor yoff,
                             doc_start, l);
 }
 
+// ---- Mamba2 recurrent decode (ssd_step.hip, causal_conv1d.hip) --------
+// Row stride of a (b, T, cols) bf16 view the step kernels read in place: a
+// last-dim slice of a projection. Unit last stride and one uniform
+// distance between the (b, t) rows, taken from b at T == 1 (the rule of
+// append_row_stride); 16-byte aligned base, stride a multiple of 8.
+static long long step_row_stride(const Tensor& t, int64_t b, int64_t T,
+                                 int64_t cols, const torch::Device& dev,
+                                 const char* op, const char* nm) {
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, op, ": ", nm,
+              " must be bf16");
+  TORCH_CHECK(t.is_cuda() && t.device() == dev, op, ": ", nm,
+              " must live on the state's GPU");
+  TORCH_CHECK(t.dim() == 3 && t.size(0) == b && t.size(1) == T &&
+                  t.size(2) == cols,
+              op, ": ", nm, " must have shape (", b, ", ", T, ", ", cols, ")");
+  TORCH_CHECK(t.stride(2) == 1, op, ": ", nm, " needs a unit last stride");
+  int64_t rs = cols;
+  if (T > 1) {
+    rs = t.stride(1);
+    TORCH_CHECK(b <= 1 || t.stride(0) == T * rs, op, ": ", nm,
+                " needs one uniform (b, t) row stride");
+  } else if (b > 1) {
+    rs = t.stride(0);
+  }
+  TORCH_CHECK(rs >= cols, op, ": ", nm, " rows overlap");
+  TORCH_CHECK(rs % 8 == 0, op, ": ", nm,
+              " row stride must be a multiple of 8 elements");
+  TORCH_CHECK(aligned16(t), op, ": ", nm, " must be 16-byte aligned");
+  return rs;
+}
+
+static void check_step_vec(const Tensor& t, int64_t n,
+                           const torch::Device& dev, const char* op,
+                           const char* nm) {
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.is_contiguous() &&
+                  t.dim() == 1 && t.numel() == n && t.is_cuda() &&
+                  t.device() == dev,
+              op, ": ", nm, " must be contiguous fp32 (", n,
+              ") on the state's GPU");
+}
+
+// T >= 1 tokens of the SSD recurrence from `state` (b, H, P, N) fp32,
+// updated in place; x/z (b, T, H*P), B/C (b, T, G*N), dt (b, T, H) bf16
+// row-strided views; returns out (b, T, H*P) bf16.
+Tensor ssd_step(Tensor state, Tensor x, Tensor dt, Tensor B, Tensor C,
+                Tensor z, Tensor dt_bias, Tensor A_log, Tensor D, int64_t H,
+                int64_t G, int64_t P, int64_t N) {
+  const char* op = "ssd_step";
+  TORCH_CHECK(state.is_cuda(), op, ": state must be on a GPU");
+  TORCH_CHECK(state.scalar_type() == torch::kFloat32, op,
+              ": state must be fp32");
+  TORCH_CHECK(N == 16 || N == 32 || N == 64 || N == 128 || N == 256, op,
+              ": d_state must be 16, 32, 64, 128 or 256, got ", N);
+  TORCH_CHECK(P > 0 && P % 8 == 0, op,
+              ": headdim must be a multiple of 8, got ", P);
+  TORCH_CHECK(H > 0 && G > 0 && H % G == 0, op,
+              ": nheads must be a multiple of ngroups, got ", H, " and ", G);
+  TORCH_CHECK(state.dim() == 4 && state.size(1) == H && state.size(2) == P &&
+                  state.size(3) == N,
+              op, ": state must have shape (b, H, P, N)");
+  TORCH_CHECK(state.is_contiguous(), op, ": state must be contiguous");
+  TORCH_CHECK(aligned16(state), op, ": state must be 16-byte aligned");
+  const int64_t b = state.size(0);
+  TORCH_CHECK(x.dim() == 3 && x.size(1) >= 1, op,
+              ": x must be (b, T, H*P) with T >= 1");
+  const int64_t T = x.size(1);
+  const auto dev = state.device();
+  const long long sx = step_row_stride(x, b, T, H * P, dev, op, "x");
+  const long long sz = step_row_stride(z, b, T, H * P, dev, op, "z");
+  const long long sB = step_row_stride(B, b, T, G * N, dev, op, "B");
+  const long long sC = step_row_stride(C, b, T, G * N, dev, op, "C");
+  // dt rows are read one bf16 at a time: any stride and alignment do
+  TORCH_CHECK(dt.scalar_type() == torch::kBFloat16 && dt.is_cuda() &&
+                  dt.device() == dev && dt.dim() == 3 && dt.size(0) == b &&
+                  dt.size(1) == T && dt.size(2) == H && dt.stride(2) == 1,
+              op, ": dt must be a bf16 (b, T, H) view with a unit last "
+              "stride on the state's GPU");
+  long long sdt = H;
+  if (T > 1) {
+    sdt = dt.stride(1);
+    TORCH_CHECK(b <= 1 || dt.stride(0) == T * sdt, op,
+                ": dt needs one uniform (b, t) row stride");
+  } else if (b > 1) {
+    sdt = dt.stride(0);
+  }
+  TORCH_CHECK(sdt >= H, op, ": dt rows overlap");
+  check_step_vec(dt_bias, H, dev, op, "dt_bias");
+  check_step_vec(A_log, H, dev, op, "A_log");
+  check_step_vec(D, H, dev, op, "D");
+  TORCH_CHECK(T < (1LL << 31) && H * P < (1LL << 31) &&
+                  G * N < (1LL << 31) &&
+                  b * H * ((P + 15) / 16) < (1LL << 31),
+              op, ": too many rows for one grid");
+  auto out = torch::empty({b, T, H * P},
+                          state.options().dtype(torch::kBFloat16));
+  if (b == 0) return out;
+  launch_ssd_step(state.data_ptr<float>(), x.data_ptr(), dt.data_ptr(),
+                  B.data_ptr(), C.data_ptr(), z.data_ptr(),
+                  dt_bias.data_ptr<float>(), A_log.data_ptr<float>(),
+                  D.data_ptr<float>(), out.data_ptr(), b, (int)T, (int)H,
+                  (int)G, (int)P, (int)N, sx, sdt, sB, sC, sz, cur_stream());
+  return out;
+}
+
+// T >= 1 rows of the causal conv behind conv_state (b, W-1, C) bf16, which
+// is updated in place; x (b, T, C) row-strided; returns y (b, T, C).
+Tensor cconv_update(Tensor conv_state, Tensor x, Tensor w, Tensor bias) {
+  const char* op = "cconv_update";
+  TORCH_CHECK(conv_state.is_cuda(), op, ": conv_state must be on a GPU");
+  TORCH_CHECK(conv_state.scalar_type() == torch::kBFloat16, op,
+              ": conv_state must be bf16");
+  TORCH_CHECK(conv_state.dim() == 3 && conv_state.is_contiguous(), op,
+              ": conv_state must be contiguous (b, W-1, C)");
+  TORCH_CHECK(aligned16(conv_state), op,
+              ": conv_state must be 16-byte aligned");
+  const auto dev = conv_state.device();
+  const int64_t b = conv_state.size(0), c = conv_state.size(2);
+  TORCH_CHECK(w.scalar_type() == torch::kBFloat16 && w.is_contiguous() &&
+                  w.dim() == 2 && w.size(0) == c && w.is_cuda() &&
+                  w.device() == dev && aligned16(w),
+              op, ": w must be contiguous bf16 (C, W) on the state's GPU");
+  const int64_t W = w.size(1);
+  TORCH_CHECK(W >= 2 && W <= 4, op, ": width must be 2, 3 or 4, got ", W);
+  TORCH_CHECK(conv_state.size(1) == W - 1, op,
+              ": conv_state must hold W-1 rows");
+  TORCH_CHECK(c > 0 && c % 8 == 0, op,
+              ": channels must be a multiple of 8, got ", c);
+  TORCH_CHECK(x.dim() == 3 && x.size(1) >= 1, op,
+              ": x must be (b, T, C) with T >= 1");
+  const int64_t T = x.size(1);
+  const long long sx = step_row_stride(x, b, T, c, dev, op, "x");
+  check_step_vec(bias, c, dev, op, "bias");
+  TORCH_CHECK(aligned16(bias), op, ": bias must be 16-byte aligned");
+  TORCH_CHECK(T < (1LL << 31) && b * (c / 8) < (1LL << 31) * 256, op,
+              ": too many elements for one grid");
+  auto y = torch::empty({b, T, c}, conv_state.options());
+  if (b == 0) return y;
+  launch_cconv_update(conv_state.data_ptr(), x.data_ptr(), w.data_ptr(),
+                      bias.data_ptr<float>(), y.data_ptr(), b, (int)T, (int)c,
+                      (int)W, sx, cur_stream());
+  return y;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("ssd_step", &ssd_step);
+  mod.def("cconv_update", &cconv_update);
   mod.def("segsum_exp_fwd", &segsum_exp_fwd);
   mod.def("segsum_exp_bwd", &segsum_exp_bwd);
   mod.def("cconv_fwd", &cconv_fwd);

@@ -296,7 +296,88 @@ __global__ void cconv_bwd_dwdb_kernel(const short* __restrict__ g,
   }
 }
 
+// Recurrent decode: T new rows behind a carried conv state. state
+// (b, W-1, C) holds the last W-1 RAW inputs of the sequence, oldest first
+// (zeros for a fresh one); x (b, T, C) is row-strided (row b*T + t at
+// that many times sx elements). Writes y = silu(conv + bias) over
+// [state | x] and leaves the last W-1 rows of [state | x] in the state,
+// for T < W-1 and T >= W-1 alike. One thread owns 8 channels for all T
+// rows with the W-deep window in registers (shifted, so every index is
+// static); channels are independent, so the in-place state update needs
+// no synchronisation. The accumulation chain is cconv_fwd_kernel's (bias
+// first, taps in wi order, the same silu): y equals cconv_fwd on the
+// concatenated sequence bit for bit, a zero state row standing in for a
+// tap in front of the row.
+template <int W>
+__global__ void cconv_update_kernel(short* __restrict__ state,
+                                    const short* __restrict__ x,
+                                    const short* __restrict__ w,
+                                    const float* __restrict__ bias,
+                                    short* __restrict__ y, int T, int C,
+                                    long long sx, long long nthr) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nthr) return;
+  const int C8 = C / 8;
+  const int c0 = (int)(i % C8) * 8;
+  const long long b_ = i / C8;
+  short* sb = state + b_ * (W - 1) * (long long)C + c0;
+  const short* xb = x + b_ * T * sx + c0;
+  short* yb = y + b_ * T * (long long)C + c0;
+  float wf[8][W];
+  unpack_wb<W>(w, c0, wf);
+  const f32x4 bv0 = *(const f32x4*)(bias + c0);
+  const f32x4 bv1 = *(const f32x4*)(bias + c0 + 4);
+  float bb[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) bb[j] = j < 4 ? bv0.v[j] : bv1.v[j - 4];
+  // win[wi] is the tap of weight wi: rows t-(W-1) .. t of [state | x]
+  float win[W][8];
+#pragma unroll
+  for (int k = 0; k < W - 1; ++k)
+    load_row8(sb + (long long)k * C, win[k + 1]);
+  for (int t = 0; t < T; ++t) {
+#pragma unroll
+    for (int k = 0; k < W - 1; ++k)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) win[k][j] = win[k + 1][j];
+    load_row8(xb + (long long)t * sx, win[W - 1]);
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float acc = bb[j];
+#pragma unroll
+      for (int wi = 0; wi < W; ++wi) acc += wf[j][wi] * win[wi][j];
+      const float s = 1.f / (1.f + __expf(-acc));
+      o.v[j] = f2bf(acc * s);
+    }
+    *(bf16x8*)(yb + (long long)t * C) = o;
+  }
+#pragma unroll
+  for (int k = 0; k < W - 1; ++k) {
+    bf16x8 o;   // raw bf16 inputs: the float round trip is exact
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o.v[j] = f2bf(win[k + 1][j]);
+    *(bf16x8*)(sb + (long long)k * C) = o;
+  }
+}
+
 extern "C" {
+
+void launch_cconv_update(void* state, const void* x, const void* w,
+                         const float* bias, void* y, long long B, int T,
+                         int C, int W, long long sx, hipStream_t stream) {
+  const long long nthr = B * (C / 8);
+  const int block = 256;
+  const int grid = (int)((nthr + block - 1) / block);
+#define CCONV_UPD(WV)                                                       \
+  cconv_update_kernel<WV><<<grid, block, 0, stream>>>(                      \
+      (short*)state, (const short*)x, (const short*)w, bias, (short*)y, T,  \
+      C, sx, nthr)
+  if (W == 4) CCONV_UPD(4);
+  else if (W == 3) CCONV_UPD(3);
+  else CCONV_UPD(2);
+#undef CCONV_UPD
+}
 
 // dstart / dend (flat (b*L) int32, ops.DocMask) select the DOCMASK
 // instantiations; nullptr is the unmasked kernel.

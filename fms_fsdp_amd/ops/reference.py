@@ -227,6 +227,53 @@ def ssd_ygate(ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q, doc_mask=None):
     return (y * zh * torch.sigmoid(zh)).reshape(rows, H * P)
 
 
+# --------------------------------------------------------------------------
+# Recurrent decode (ops/hip/ssd_step.hip, cconv_update_kernel): the oracles
+# of _C.ssd_step and _C.cconv_update, same signatures, states updated in
+# place. float64 inputs compute in float64, everything else in fp32.
+# --------------------------------------------------------------------------
+def causal_conv1d_update(conv_state, x, weight, bias):
+    """T new rows x (b, T, C) behind conv_state (b, W-1, C), the last W-1
+    raw inputs, oldest first (zeros = a fresh sequence): returns
+    silu(conv + bias) over [state | x] for the new rows and leaves the
+    last W-1 rows of [state | x] in conv_state."""
+    W = weight.shape[1]
+    full = torch.cat([conv_state.to(x.dtype), x], dim=1)
+    y = causal_conv1d(full, weight, bias)[:, W - 1:]
+    conv_state.copy_(full[:, full.shape[1] - (W - 1):])
+    return y
+
+
+def ssd_state_update(state, x, dt, B, C, z, dt_bias, A_log, D, H, G, P, N):
+    """The SSD recurrence over T >= 1 tokens from `state` (b, H, P, N),
+    which ends as the state after the last token. x/z (b, T, H*P), B/C
+    (b, T, G*N), dt (b, T, H) raw; dt_bias/A_log/D (H). Per token:
+      dtf = softplus(dt + dt_bias); a = exp(dtf * -exp(A_log))
+      s = a*s + (dtf*x) B^T; y = s C + D*x; out = y * silu(z)
+    Returns out (b, T, H*P) in x's dtype."""
+    b, T, _ = x.shape
+    ct = torch.float64 if x.dtype == torch.float64 else torch.float32
+    rep = H // G
+    xh = x.to(ct).reshape(b, T, H, P)
+    zh = z.to(ct).reshape(b, T, H, P)
+    Bh = B.to(ct).reshape(b, T, G, N).repeat_interleave(rep, dim=2)
+    Ch = C.to(ct).reshape(b, T, G, N).repeat_interleave(rep, dim=2)
+    xs = dt.to(ct) + dt_bias.to(ct)
+    dtf = torch.logaddexp(xs, torch.zeros_like(xs))            # (b, T, H)
+    a = torch.exp(dtf * -torch.exp(A_log.to(ct)))
+    Dh = D.to(ct).view(1, H, 1)
+    s = state.to(ct)
+    ys = []
+    for t in range(T):
+        xdt = dtf[:, t, :, None] * xh[:, t]                    # (b, H, P)
+        s = a[:, t, :, None, None] * s \
+            + xdt[..., None] * Bh[:, t, :, None, :]
+        ys.append((s * Ch[:, t, :, None, :]).sum(-1) + Dh * xh[:, t])
+    state.copy_(s)
+    y = torch.stack(ys, dim=1)                                 # (b, T, H, P)
+    return (y * zh * torch.sigmoid(zh)).reshape(b, T, H * P).to(x.dtype)
+
+
 def adamw_step(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay):
     """In-place fp32 AdamW on flat tensors (the shard update)."""
     p.mul_(1 - lr * weight_decay)

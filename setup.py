@@ -21,7 +21,8 @@ BUILD_DIR = os.path.join(REPO, "build", "hip_objs")
 
 HIP_SOURCES = ["rmsnorm.hip", "rope.hip", "swiglu.hip", "cross_entropy.hip",
                "adamw.hip", "attention.hip", "causal_conv1d.hip", "ssd.hip",
-               "gemm_nt.hip", "transpose.hip", "attn_decode.hip"]
+               "gemm_nt.hip", "transpose.hip", "attn_decode.hip",
+               "ssd_step.hip"]
 # headers the .hip sources include: a newer header rebuilds every object
 HIP_HEADERS = ["common.h", "attn_sched.h", "attn_ws.h", "attn_frag.h",
                "attn_decode_plan.h"]
