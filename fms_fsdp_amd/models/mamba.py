@@ -253,14 +253,15 @@ class Mamba2Mixer(nn.Module):
     def _scan_fused(self, b, l, x, dt, z, B, C, dtb, Alog, D_,
                     doc_start=None, doc_end=None, return_final_state=False):
         """GPU SSD scan: the elementwise chains run as fused HIP kernels
-        (ops/hip/ssd.hip — prep/xdt/scores-decay/ygate, each with a
-        custom backward); only the MFMA-shaped work (scores, y_diag,
-        states, y_off einsums on hipBLASLt) and the tiny nc x nc
+        (ops/hip/ssd.hip — prep/xdt/ygate, each with a custom backward),
+        the intra-chunk term y_diag as the fused MFMA kernel of
+        ops/hip/ssd_diag.hip; only the other MFMA-shaped work (states,
+        y_off einsums on hipBLASLt) and the tiny nc x nc
         inter-chunk recurrence stay as torch ops. Inputs x/dt/z/B/C are
         STRIDED slices of the fused projections — no contiguous copies.
         Returns the gated (b, l, d_inner) bf16 activations (pre-norm).
         doc_start/doc_end (a DocMask's arrays) reset the scan at every
-        document start: masked xdt / scores-decay / ygate kernels plus a
+        document start: masked xdt / y_diag / ygate kernels plus a
         select on the inter-chunk matrix (see ssd_chunked).
         return_final_state: also the fp32 (b, h, p, n) state after the last
         token (see ssd_chunked)."""
@@ -279,15 +280,14 @@ class Mamba2Mixer(nn.Module):
         # strided-batched bmm and no einsum materializes permuted copies
         xdt, xdtd = ops.ssd_xdt(x2, dtf, dacs, h, p, Q,    # bf16 pair
                                 doc_mask=doc_mask)
-        N = b * nc * h
         Bm = B.reshape(b, nc, Q, g, n)
         Cm = C.reshape(b, nc, Q, g, n)
-        # scores per GROUP (g << h), decay folded in-kernel (L never
-        # materialized; d_scores comes back from the fused backward)
-        scores = torch.einsum("bcqgn,bckgn->bcgqk", Cm, Bm).contiguous()
-        sL = ops.ssd_scores_decay(dacs, scores.view(b * nc * g, Q, Q), h, g,
-                                  doc_mask=doc_mask)
-        y_diag = torch.bmm(sL, xdt.view(N, Q, p))          # (N, Q, p) bf16
+        # intra-chunk term: scores per GROUP (g << h), decay and the
+        # product with xdt in one kernel (ops/hip/ssd_diag.hip; neither
+        # the scores nor sL reach HBM). B/C are read in place.
+        y_diag = ops.ssd_diag(C.reshape(b * l, g * n), B.reshape(b * l, g * n),
+                              dacs, xdt, h, g, p, n, Q,
+                              doc_mask=doc_mask)           # (N, Q, p) bf16
         # the whole inter-chunk state chain runs bf16 (W entries are
         # decays in [0,1], states are sums of bf16-rounded products with
         # fp32 GEMM accumulation) — halves the traffic of the biggest

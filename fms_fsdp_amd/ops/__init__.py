@@ -1198,6 +1198,90 @@ def ssd_scores_decay(dacs, scores3d, H, G, doc_mask=None):
         dacs, scores3d, H, G, *_doc_start_arg(doc_mask, N // H * Q, Q))
 
 
+def _ssd_diag_gemm(C2d, B2d, dacs, xdt, H, G, P, N, Q, doc_mask):
+    """y_diag in three launches: per-group scores (hipBLASLt), the fused
+    scores*decay kernel, the bmm; sL (bc*H, Q, Q) goes through HBM."""
+    bc = C2d.shape[0] // Q
+    Cm = C2d.view(bc, Q, G, N)
+    Bm = B2d.view(bc, Q, G, N)
+    scores = torch.einsum("cqgn,ckgn->cgqk", Cm, Bm).contiguous()
+    sL = ssd_scores_decay(dacs, scores.view(bc * G, Q, Q), H, G,
+                          doc_mask=doc_mask)
+    return torch.bmm(sL, xdt.view(bc * H, Q, P))
+
+
+class _SSDDiagFn(torch.autograd.Function):
+    """y_diag (bc*H, Q, P) from ops/hip/ssd_diag.hip: scores, decay and the
+    second product in one kernel, sL never written. The backward is the
+    three-launch route's own: scores and sL are recomputed from the saved
+    inputs, the bmm's two gradients are taken as autograd takes them, and
+    dC / dB / ddacs come from that route's graph (ssd_sl_bwd, the group
+    sum, the two score GEMMs)."""
+
+    @staticmethod
+    def forward(ctx, C2d, B2d, dacs, xdt, H, G, P, N, Q, doc_mask=None):
+        ext = _require_ext("ssd_diag")
+        doc = _doc_start_arg(doc_mask, C2d.shape[0], Q)
+        if doc:
+            y = ext.ssd_diag_fwd_doc(C2d, B2d, dacs, xdt, H, G, P, N, Q,
+                                     doc[0], doc[0].shape[-1])
+        else:
+            y = ext.ssd_diag_fwd(C2d, B2d, dacs, xdt, H, G, P, N, Q)
+        ctx.save_for_backward(C2d, B2d, dacs, xdt)
+        ctx.meta = (H, G, P, N, Q, doc_mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        C2d, B2d, dacs, xdt = ctx.saved_tensors
+        H, G, P, N, Q, doc_mask = ctx.meta
+        bc = C2d.shape[0] // Q
+        with torch.enable_grad():
+            Cd = C2d.detach().requires_grad_()
+            Bd = B2d.detach().requires_grad_()
+            cs = dacs.detach().requires_grad_()
+            scores = torch.einsum(
+                "cqgn,ckgn->cgqk", Cd.view(bc, Q, G, N),
+                Bd.view(bc, Q, G, N)).contiguous()
+            sL = ssd_scores_decay(cs, scores.view(bc * G, Q, Q), H, G,
+                                  doc_mask=doc_mask)
+        x3 = xdt.view(bc * H, Q, P)
+        dsL = dy.bmm(x3.transpose(1, 2))
+        dxdt = sL.detach().transpose(1, 2).bmm(dy)
+        dC, dB, dcs = torch.autograd.grad(sL, (Cd, Bd, cs), dsL)
+        return (dC, dB, dcs, dxdt.view_as(xdt)) + (None,) * 6
+
+
+def _ssd_diag_view(t):
+    """A (b*l, G*N) slice as the kernel reads it without a copy (the rule of
+    _step_view): unit last stride, row stride a multiple of 8 elements,
+    16-byte aligned base."""
+    ok = (t.stride(1) == 1 and t.stride(0) >= t.shape[1]
+          and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0)
+    return t if ok else t.contiguous()
+
+
+def ssd_diag(C2d, B2d, dacs, xdt, H, G, P, N, Q, doc_mask=None):
+    """Intra-chunk term of the SSD, (b*l/Q*H, Q, P) h-major: y[n, i] =
+    sum_{j<=i} (C_i . B_j) exp(dacs[n, i] - dacs[n, j]) xdt[n, j]
+    (reference.ssd_diag has the definition). C2d/B2d (b*l, G*N) may be
+    last-dim slices of the conv output; dacs (n, Q) fp32 from ssd_prep, xdt
+    h-major bf16 from ssd_xdt. On the GPU the supported shapes (N and P
+    with an instantiation, Q a multiple of 32 up to 256) run the fused
+    kernel of ops/hip/ssd_diag.hip; every other shape, and every shape
+    under FMS_AMD_SSD_DIAG=gemm, takes the three-launch route."""
+    if not dacs.is_cuda:
+        return reference.ssd_diag(C2d, B2d, dacs, xdt, H, G, P, N, Q,
+                                  doc_mask)
+    ext = _require_ext("ssd_diag")
+    if os.environ.get("FMS_AMD_SSD_DIAG") == "gemm" \
+            or C2d.dtype != torch.bfloat16 \
+            or not ext.ssd_diag_has_kernel(N, P, Q):
+        return _ssd_diag_gemm(C2d, B2d, dacs, xdt, H, G, P, N, Q, doc_mask)
+    return _SSDDiagFn.apply(_ssd_diag_view(C2d), _ssd_diag_view(B2d), dacs,
+                            xdt.contiguous(), H, G, P, N, Q, doc_mask)
+
+
 class _SSDYGateFn(torch.autograd.Function):
     """out = (ydiag + yoff*exp(dacs) + x*D) * silu(z), bf16 in one pass
     (y assembly + D residual + the gated epilogue)."""

@@ -103,6 +103,10 @@ void launch_ssd_ygate_bwd(const void*, const void*, const void*, const float*,
                           long long, const int*, int, hipStream_t);
 void launch_cconv_update(void*, const void*, const void*, const float*, void*,
                          long long, int, int, int, long long, hipStream_t);
+int ssd_diag_supported(int, int);
+void launch_ssd_diag_fwd(const void*, const void*, const float*, const void*,
+                         void*, long long, int, int, int, int, int, long long,
+                         long long, const int*, int, hipStream_t);
 void launch_ssd_step(float*, const void*, const void*, const void*,
                      const void*, const void*, const float*, const float*,
                      const float*, void*, long long, int, int, int, int, int,
@@ -1165,6 +1169,79 @@ std::tuple<Tensor, Tensor> ssd_sl_bwd_doc(Tensor g, Tensor scores,
   return ssd_sl_bwd_impl(g, scores, dacs, H, G, doc_start, l);
 }
 
+// ---- fused intra-chunk SSD term (ssd_diag.hip) -------------------------
+// C / B: (b*l, G*N) bf16 last-dim slices read in place (unit last stride,
+// row stride a multiple of 8 elements, 16-byte aligned base); returns the
+// row stride
+static long long check_diag_slice(const Tensor& t, long long rows,
+                                  long long cols, const Tensor& like,
+                                  const char* nm) {
+  const long long st = slice_stride(t, nm);
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), nm,
+              " must be on the GPU of dacs");
+  TORCH_CHECK(t.size(0) == rows && t.size(1) == cols, nm,
+              " must have shape (b*l, G*N)");
+  TORCH_CHECK(st >= cols && st % 8 == 0 && aligned16(t), nm,
+              " needs a row stride that is a multiple of 8 elements and a "
+              "16-byte aligned base");
+  return st;
+}
+
+static int64_t ssd_diag_count = 0;
+
+static Tensor ssd_diag_fwd_impl(Tensor C, Tensor B, Tensor dacs, Tensor xdt,
+                                int64_t H, int64_t G, int64_t P, int64_t N,
+                                int64_t Q, c10::optional<Tensor> doc_start,
+                                int64_t l) {
+  TORCH_CHECK(H > 0 && G > 0 && H % G == 0, "H must be a multiple of G");
+  TORCH_CHECK(N > 0 && P > 0 && ssd_diag_supported((int)N, (int)P),
+              "ssd_diag: no kernel for N = ", N, ", P = ", P);
+  TORCH_CHECK(Q >= 32 && Q <= 256 && Q % 32 == 0,
+              "ssd_diag: Q must be a multiple of 32 in [32, 256], got ", Q);
+  TORCH_CHECK(dacs.is_cuda() && dacs.dim() == 2, "dacs must be (N, Q) on a GPU");
+  TORCH_CHECK(C.dim() == 2 && C.size(0) % Q == 0,
+              "C rows must be a multiple of Q");
+  const long long rows = C.size(0);
+  const long long nrows = rows / Q * H;
+  check_nq(dacs, nrows, Q, "dacs");
+  const long long sC = check_diag_slice(C, rows, G * N, dacs, "C");
+  const long long sB = check_diag_slice(B, rows, G * N, dacs, "B");
+  check_bf16_numel(xdt, rows * H * P, "xdt");
+  TORCH_CHECK(xdt.device() == dacs.device(), "xdt must be on the GPU of dacs");
+  const int* ds = doc_ptr(doc_start, rows, dacs, "doc_start");
+  const int nc = ds ? doc_nc(rows, l, Q) : 1;
+  TORCH_CHECK(nrows * ((Q + 127) / 128) < (1LL << 31),
+              "ssd_diag: too many rows for one grid");
+  auto y = torch::empty({nrows, Q, P}, xdt.options());
+  if (nrows == 0) return y;
+  launch_ssd_diag_fwd(C.data_ptr(), B.data_ptr(), dacs.data_ptr<float>(),
+                      xdt.data_ptr(), y.data_ptr(), nrows, (int)H, (int)G,
+                      (int)P, (int)N, (int)Q, sC, sB, ds, nc, cur_stream());
+  ++ssd_diag_count;
+  return y;
+}
+
+Tensor ssd_diag_fwd(Tensor C, Tensor B, Tensor dacs, Tensor xdt, int64_t H,
+                    int64_t G, int64_t P, int64_t N, int64_t Q) {
+  return ssd_diag_fwd_impl(C, B, dacs, xdt, H, G, P, N, Q, c10::nullopt, 0);
+}
+
+Tensor ssd_diag_fwd_doc(Tensor C, Tensor B, Tensor dacs, Tensor xdt,
+                        int64_t H, int64_t G, int64_t P, int64_t N, int64_t Q,
+                        Tensor doc_start, int64_t l) {
+  return ssd_diag_fwd_impl(C, B, dacs, xdt, H, G, P, N, Q, doc_start, l);
+}
+
+// Launches of the fused kernel so far: lets a test see which route ran.
+int64_t ssd_diag_calls() { return ssd_diag_count; }
+
+// whether ops.ssd_diag may send (N, P, Q) to the kernel
+bool ssd_diag_has_kernel(int64_t N, int64_t P, int64_t Q) {
+  return N > 0 && P > 0 && N <= 256 && P <= 256 &&
+         ssd_diag_supported((int)N, (int)P) && Q >= 32 && Q <= 256 &&
+         Q % 32 == 0;
+}
+
 static void check_ygate(const Tensor& ydiag, const Tensor& yoff,
                         const Tensor& dacs, const Tensor& x, const Tensor& Dp,
                         const Tensor& z, int64_t H, int64_t G, int64_t Q) {
@@ -1438,6 +1515,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ssd_xdt_bwd_doc", &ssd_xdt_bwd_doc);
   mod.def("ssd_sl_fwd_doc", &ssd_sl_fwd_doc);
   mod.def("ssd_sl_bwd_doc", &ssd_sl_bwd_doc);
+  mod.def("ssd_diag_fwd", &ssd_diag_fwd);
+  mod.def("ssd_diag_fwd_doc", &ssd_diag_fwd_doc);
+  mod.def("ssd_diag_calls", &ssd_diag_calls);
+  mod.def("ssd_diag_has_kernel", &ssd_diag_has_kernel);
   mod.def("ssd_ygate_fwd_doc", &ssd_ygate_fwd_doc);
   mod.def("ssd_ygate_bwd_doc", &ssd_ygate_bwd_doc);
   mod.def("attn_fwd", &attn_fwd);

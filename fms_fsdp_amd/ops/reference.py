@@ -206,6 +206,20 @@ def ssd_scores_decay(dacs, scores3d, H, G, doc_mask=None):
     return s.reshape(N, Q, Q) * L
 
 
+def ssd_diag(C2d, B2d, dacs, xdt, H, G, P, N, Q, doc_mask=None):
+    """The intra-chunk term y_diag (bc*H, Q, P) of the scan (oracle of
+    ops/hip/ssd_diag.hip): y[n, i] = sum_{j<=i} (C_i . B_j) exp(dacs[n, i]
+    - dacs[n, j]) xdt[n, j], the per-group scores einsum, ssd_scores_decay
+    and the matmul composed. C2d/B2d (b*l, G*N); xdt h-major (bc, H, Q, P)
+    in any shape with that element order."""
+    bc = C2d.shape[0] // Q
+    Cm = C2d.reshape(bc, Q, G, N)
+    Bm = B2d.reshape(bc, Q, G, N)
+    scores = torch.einsum("cqgn,ckgn->cgqk", Cm, Bm).reshape(bc * G, Q, Q)
+    sL = ssd_scores_decay(dacs, scores, H, G, doc_mask)
+    return torch.matmul(sL, xdt.reshape(bc * H, Q, P))
+
+
 def ssd_ygate(ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q, doc_mask=None):
     """out = (ydiag + yoff*exp(dacs) + x*D) * silu(z), (b*l, H*P).
     ydiag h-major (bc, H, Q, P); yoff (bc, G, Q, rep, P). doc_mask: the

@@ -22,7 +22,11 @@ BUILD_DIR = os.path.join(REPO, "build", "hip_objs")
 HIP_SOURCES = ["rmsnorm.hip", "rope.hip", "swiglu.hip", "cross_entropy.hip",
                "adamw.hip", "attention.hip", "causal_conv1d.hip", "ssd.hip",
                "gemm_nt.hip", "transpose.hip", "attn_decode.hip",
-               "ssd_step.hip"]
+               "ssd_step.hip", "ssd_diag.hip"]
+# extra hipcc flags per source: ssd_diag.hip is built without the packed
+# fp32 VALU forms
+HIP_EXTRA_FLAGS = {"ssd_diag.hip": ["-Xclang", "-target-feature", "-Xclang",
+                                    "-packed-fp32-ops"]}
 # headers the .hip sources include: a newer header rebuilds every object
 HIP_HEADERS = ["common.h", "attn_sched.h", "attn_ws.h", "attn_frag.h",
                "attn_decode_plan.h"]
@@ -40,6 +44,7 @@ def compile_hip_objects():
                        for d in deps)):
             cmd = [os.path.join(ROCM, "bin", "hipcc"),
                    f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
+                   *HIP_EXTRA_FLAGS.get(src, []),
                    "-c", src_path, "-o", obj_path]
             print(" ".join(cmd))
             subprocess.check_call(cmd)
