@@ -116,3 +116,8 @@ class train_config:
     # the hybrid: the SSM state and the causal conv restart at every
     # document start, and the hybrid's attention layers take the same mask.
     doc_mask: bool = False
+    # Backward of the Mamba2 intra-chunk term y_diag: "gemm" recomputes the
+    # three-launch route (scores, sL and dS go through HBM), "fused" runs
+    # the two-pass kernel of ops/hip/ssd_diag_bwd.hip. Applied once at
+    # start-up through ops.ssd_diag_backward().
+    ssd_diag_bwd: str = "gemm"

@@ -1210,13 +1210,39 @@ def _ssd_diag_gemm(C2d, B2d, dacs, xdt, H, G, P, N, Q, doc_mask):
     return torch.bmm(sL, xdt.view(bc * H, Q, P))
 
 
+_SSD_DIAG_BWD_MODES = ("gemm", "fused")
+_ssd_diag_bwd_mode = None
+
+
+def ssd_diag_backward(mode=None):
+    """Get/set the process-wide backward of the fused ssd_diag op: "gemm"
+    (default) recomputes the three-launch route, "fused" runs the two-pass
+    kernel of ops/hip/ssd_diag_bwd.hip. None = query. Returns the previous
+    mode; until it is set, FMS_AMD_SSD_DIAG_BWD gives the mode."""
+    global _ssd_diag_bwd_mode
+    prev = _ssd_diag_bwd_mode
+    if prev is None:
+        prev = os.environ.get("FMS_AMD_SSD_DIAG_BWD") or "gemm"
+        if prev not in _SSD_DIAG_BWD_MODES:
+            raise ValueError(f"FMS_AMD_SSD_DIAG_BWD must be one of "
+                             f"{_SSD_DIAG_BWD_MODES}, got {prev!r}")
+    if mode is not None:
+        if mode not in _SSD_DIAG_BWD_MODES:
+            raise ValueError(f"ssd_diag_backward: mode must be one of "
+                             f"{_SSD_DIAG_BWD_MODES}, got {mode!r}")
+        _ssd_diag_bwd_mode = mode
+    return prev
+
+
 class _SSDDiagFn(torch.autograd.Function):
     """y_diag (bc*H, Q, P) from ops/hip/ssd_diag.hip: scores, decay and the
-    second product in one kernel, sL never written. The backward is the
-    three-launch route's own: scores and sL are recomputed from the saved
-    inputs, the bmm's two gradients are taken as autograd takes them, and
-    dC / dB / ddacs come from that route's graph (ssd_sl_bwd, the group
-    sum, the two score GEMMs)."""
+    second product in one kernel, sL never written. The backward depends on
+    ssd_diag_backward(). "gemm" is the three-launch route's own: scores and
+    sL are recomputed from the saved inputs, the bmm's two gradients are
+    taken as autograd takes them, and dC / dB / ddacs come from that route's
+    graph (ssd_sl_bwd, the group sum, the two score GEMMs). "fused" is
+    ops/hip/ssd_diag_bwd.hip: nothing quadratic in Q reaches HBM, and dC /
+    dB arrive as fp32 partials per head block that are summed here."""
 
     @staticmethod
     def forward(ctx, C2d, B2d, dacs, xdt, H, G, P, N, Q, doc_mask=None):
@@ -1236,6 +1262,19 @@ class _SSDDiagFn(torch.autograd.Function):
         C2d, B2d, dacs, xdt = ctx.saved_tensors
         H, G, P, N, Q, doc_mask = ctx.meta
         bc = C2d.shape[0] // Q
+        if ssd_diag_backward() == "fused":
+            ext = _require_ext("ssd_diag_bwd")
+            dy = dy.contiguous()
+            doc = _doc_start_arg(doc_mask, C2d.shape[0], Q)
+            if doc:
+                dCp, dBp, dcs, dxdt = ext.ssd_diag_bwd_doc(
+                    dy, C2d, B2d, dacs, xdt, H, G, P, N, Q, doc[0],
+                    doc[0].shape[-1])
+            else:
+                dCp, dBp, dcs, dxdt = ext.ssd_diag_bwd(
+                    dy, C2d, B2d, dacs, xdt, H, G, P, N, Q)
+            return (dCp.sum(0).to(C2d.dtype), dBp.sum(0).to(B2d.dtype), dcs,
+                    dxdt) + (None,) * 6
         with torch.enable_grad():
             Cd = C2d.detach().requires_grad_()
             Bd = B2d.detach().requires_grad_()
@@ -1269,7 +1308,8 @@ def ssd_diag(C2d, B2d, dacs, xdt, H, G, P, N, Q, doc_mask=None):
     h-major bf16 from ssd_xdt. On the GPU the supported shapes (N and P
     with an instantiation, Q a multiple of 32 up to 256) run the fused
     kernel of ops/hip/ssd_diag.hip; every other shape, and every shape
-    under FMS_AMD_SSD_DIAG=gemm, takes the three-launch route."""
+    under FMS_AMD_SSD_DIAG=gemm, takes the three-launch route. The fused
+    kernel's backward is chosen by ssd_diag_backward()."""
     if not dacs.is_cuda:
         return reference.ssd_diag(C2d, B2d, dacs, xdt, H, G, P, N, Q,
                                   doc_mask)

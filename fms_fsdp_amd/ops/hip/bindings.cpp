@@ -104,6 +104,11 @@ void launch_ssd_ygate_bwd(const void*, const void*, const void*, const float*,
 void launch_cconv_update(void*, const void*, const void*, const float*, void*,
                          long long, int, int, int, long long, hipStream_t);
 int ssd_diag_supported(int, int);
+int ssd_diag_bwd_plan(long long, int, int, int);
+void launch_ssd_diag_bwd(const void*, const void*, const void*, const float*,
+                         const void*, float*, float*, float*, void*,
+                         long long, int, int, int, int, int, long long,
+                         long long, int, const int*, int, hipStream_t);
 void launch_ssd_diag_fwd(const void*, const void*, const float*, const void*,
                          void*, long long, int, int, int, int, int, long long,
                          long long, const int*, int, hipStream_t);
@@ -1242,6 +1247,103 @@ bool ssd_diag_has_kernel(int64_t N, int64_t P, int64_t Q) {
          Q % 32 == 0;
 }
 
+// ---- fused backward of the intra-chunk term (ssd_diag_bwd.hip) ---------
+// Workgroups per CU the head-block plan aims for (docs/performance.md).
+constexpr int SSD_DIAG_BWD_WGS_PER_CU = 2;
+
+static int64_t ssd_diag_bwd_count = 0;
+
+// compute units of a device, queried once per device
+static int ssd_diag_bwd_cus(int dev) {
+  static std::vector<int> cus;
+  if (dev >= (int)cus.size()) cus.resize(dev + 1, 0);
+  if (cus[dev] == 0) {
+    TORCH_CHECK(hipDeviceGetAttribute(&cus[dev],
+                                      hipDeviceAttributeMultiprocessorCount,
+                                      dev) == hipSuccess && cus[dev] > 0,
+                "ssd_diag_bwd: cannot query the compute unit count");
+  }
+  return cus[dev];
+}
+
+// dy (bc*H, Q, P) bf16 contiguous; the other arguments as ssd_diag_fwd.
+// Returns (dC partials, dB partials) (nhb, b*l, G*N) fp32, to be summed
+// over dim 0, ddacs (bc*H, Q) fp32 and dxdt bf16 in xdt's shape.
+// head_blocks = 0 takes the plan.
+static std::tuple<Tensor, Tensor, Tensor, Tensor> ssd_diag_bwd_impl(
+    Tensor dy, Tensor C, Tensor B, Tensor dacs, Tensor xdt, int64_t H,
+    int64_t G, int64_t P, int64_t N, int64_t Q, int64_t head_blocks,
+    c10::optional<Tensor> doc_start, int64_t l) {
+  TORCH_CHECK(H > 0 && G > 0 && H % G == 0, "H must be a multiple of G");
+  TORCH_CHECK(N > 0 && P > 0 && ssd_diag_supported((int)N, (int)P),
+              "ssd_diag_bwd: no kernel for N = ", N, ", P = ", P);
+  TORCH_CHECK(Q >= 32 && Q <= 256 && Q % 32 == 0,
+              "ssd_diag_bwd: Q must be a multiple of 32 in [32, 256], got ",
+              Q);
+  TORCH_CHECK(head_blocks >= 0 && head_blocks <= H / G,
+              "ssd_diag_bwd: head_blocks must lie in [0, H/G], got ",
+              head_blocks);
+  TORCH_CHECK(dacs.is_cuda() && dacs.dim() == 2, "dacs must be (N, Q) on a GPU");
+  TORCH_CHECK(C.dim() == 2 && C.size(0) % Q == 0,
+              "C rows must be a multiple of Q");
+  const long long rows = C.size(0);
+  const long long nrows = rows / Q * H;
+  check_nq(dacs, nrows, Q, "dacs");
+  const long long sC = check_diag_slice(C, rows, G * N, dacs, "C");
+  const long long sB = check_diag_slice(B, rows, G * N, dacs, "B");
+  // the kernel offsets a staged tile's 64 rows in 32 bits
+  TORCH_CHECK(sC < (1LL << 24) && sB < (1LL << 24),
+              "ssd_diag_bwd: row stride of C / B too large");
+  check_bf16_numel(xdt, rows * H * P, "xdt");
+  check_bf16_numel(dy, rows * H * P, "dy");
+  TORCH_CHECK(dy.dim() == 3 && dy.size(0) == nrows && dy.size(1) == Q &&
+                  dy.size(2) == P, "dy must have shape (rows/Q*H, Q, P)");
+  TORCH_CHECK(xdt.device() == dacs.device() && dy.device() == dacs.device(),
+              "xdt and dy must be on the GPU of dacs");
+  const int* ds = doc_ptr(doc_start, rows, dacs, "doc_start");
+  const int nc = ds ? doc_nc(rows, l, Q) : 1;
+  const long long base = rows / Q * G * ((Q + 127) / 128);
+  TORCH_CHECK(base * (H / G) < (1LL << 31),
+              "ssd_diag_bwd: too many rows for one grid");
+  int nhb = (int)head_blocks;
+  if (nhb == 0)
+    nhb = ssd_diag_bwd_plan(base, (int)(H / G),
+                            ssd_diag_bwd_cus(dacs.get_device()),
+                            SSD_DIAG_BWD_WGS_PER_CU);
+  auto f32 = dacs.options();
+  auto dCp = torch::empty({nhb, rows, G * N}, f32);
+  auto dBp = torch::empty({nhb, rows, G * N}, f32);
+  auto ddacs = torch::empty({nrows, Q}, f32);
+  auto dxdt = torch::empty_like(xdt);
+  if (nrows == 0) return {dCp, dBp, ddacs, dxdt};
+  launch_ssd_diag_bwd(dy.data_ptr(), C.data_ptr(), B.data_ptr(),
+                      dacs.data_ptr<float>(), xdt.data_ptr(),
+                      dCp.data_ptr<float>(), dBp.data_ptr<float>(),
+                      ddacs.data_ptr<float>(), dxdt.data_ptr(), rows, (int)H,
+                      (int)G, (int)P, (int)N, (int)Q, sC, sB, nhb, ds, nc,
+                      cur_stream());
+  ++ssd_diag_bwd_count;
+  return {dCp, dBp, ddacs, dxdt};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> ssd_diag_bwd(
+    Tensor dy, Tensor C, Tensor B, Tensor dacs, Tensor xdt, int64_t H,
+    int64_t G, int64_t P, int64_t N, int64_t Q, int64_t head_blocks) {
+  return ssd_diag_bwd_impl(dy, C, B, dacs, xdt, H, G, P, N, Q, head_blocks,
+                           c10::nullopt, 0);
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> ssd_diag_bwd_doc(
+    Tensor dy, Tensor C, Tensor B, Tensor dacs, Tensor xdt, int64_t H,
+    int64_t G, int64_t P, int64_t N, int64_t Q, Tensor doc_start, int64_t l,
+    int64_t head_blocks) {
+  return ssd_diag_bwd_impl(dy, C, B, dacs, xdt, H, G, P, N, Q, head_blocks,
+                           doc_start, l);
+}
+
+// Calls of the fused backward so far: lets a test see which route ran.
+int64_t ssd_diag_bwd_calls() { return ssd_diag_bwd_count; }
+
 static void check_ygate(const Tensor& ydiag, const Tensor& yoff,
                         const Tensor& dacs, const Tensor& x, const Tensor& Dp,
                         const Tensor& z, int64_t H, int64_t G, int64_t Q) {
@@ -1519,6 +1621,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ssd_diag_fwd_doc", &ssd_diag_fwd_doc);
   mod.def("ssd_diag_calls", &ssd_diag_calls);
   mod.def("ssd_diag_has_kernel", &ssd_diag_has_kernel);
+  mod.def("ssd_diag_bwd", &ssd_diag_bwd, py::arg("dy"), py::arg("C"),
+          py::arg("B"), py::arg("dacs"), py::arg("xdt"), py::arg("H"),
+          py::arg("G"), py::arg("P"), py::arg("N"), py::arg("Q"),
+          py::arg("head_blocks") = 0);
+  mod.def("ssd_diag_bwd_doc", &ssd_diag_bwd_doc, py::arg("dy"), py::arg("C"),
+          py::arg("B"), py::arg("dacs"), py::arg("xdt"), py::arg("H"),
+          py::arg("G"), py::arg("P"), py::arg("N"), py::arg("Q"),
+          py::arg("doc_start"), py::arg("l"), py::arg("head_blocks") = 0);
+  mod.def("ssd_diag_bwd_calls", &ssd_diag_bwd_calls);
   mod.def("ssd_ygate_fwd_doc", &ssd_ygate_fwd_doc);
   mod.def("ssd_ygate_bwd_doc", &ssd_ygate_bwd_doc);
   mod.def("attn_fwd", &attn_fwd);

@@ -40,6 +40,7 @@ def main(**kwargs):
         torch.cuda.set_device(local_rank)
     setup_environ_flags()
     ops.attn_bwd_workspace_limit(cfg.attn_bwd_workspace_mb)
+    ops.ssd_diag_backward(cfg.ssd_diag_bwd)
 
     if rank == 0:
         print(f"--> running with these configs {cfg}")
