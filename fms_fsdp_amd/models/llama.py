@@ -209,9 +209,8 @@ class SwiGLU(nn.Module):
             h = ops.swiglu(gu)
             out = self.w2(h)
             return out if residual is None else out + residual.view_as(out)
-        gu = ops.linear_flat(x, self.wg1.weight)
-        h = ops.swiglu(gu)                         # silu(g) * u, fused kernel
-        return ops.linear_flat(h, self.w2.weight, residual)
+        # gate|up GEMM, silu(g) * u, down GEMM + residual
+        return ops.swiglu_mlp(x, self.wg1.weight, self.w2.weight, residual)
 
     def reset_parameters(self):
         for lin in (self.wg1, self.w2):

@@ -320,6 +320,16 @@ def rope_apply(q, k, cos, sin):
 # one loses, the transpose being a fixed cost. Hence the wgrad's rule:
 # tokens >= 8192 and a weight of at least 4096 x 8192 elements.
 # FMS_AMD_DGRAD=nn keeps every dgrad on the old route.
+#
+# In the MLP two of those transposes re-read what swiglu's backward has
+# just held in registers: dgu for the gate|up wgrad, and h, saved by the
+# forward, for the down wgrad. swiglu_mlp (below, after swiglu) is the MLP
+# as one autograd function whose backward gets dgu, dgu^T and h^T from one
+# kernel (_C.swiglu_bwd_t) and hands the transposed operands to
+# _C.wgrad_tn_pre: per layer two launches and 540 MB of traffic less, and
+# h is no longer saved. It runs where both wgrads and both dgrads of the
+# MLP take the TN routes above; elsewhere the MLP stays the composition
+# of linear_flat and swiglu.
 # --------------------------------------------------------------------------
 _WGRAD_TN_MIN_TOKENS = 8192
 _WGRAD_TN_MIN_WEIGHT = 4096 * 8192   # out * in
@@ -327,46 +337,57 @@ _DGRAD_TN_MIN_TOKENS = 8192
 _DGRAD_TN_MIN_WEIGHT = 4096 * 8192   # out * in
 
 
+def _transpose_reads(t):
+    """What transpose.hip reads without a copy."""
+    return not (t.stride(1) != 1 or t.stride(0) % 8
+                or t.stride(0) < t.shape[1] or t.data_ptr() % 16)
+
+
+def _wgrad_tn_shape(tokens, out, inn):
+    """The part of _wgrad_mode's rule that the shape decides."""
+    if _C is None or os.environ.get("FMS_AMD_WGRAD") == "nt":
+        return False
+    if tokens % 8 or out % 8 or inn % 8:
+        return False
+    return (tokens >= _WGRAD_TN_MIN_TOKENS
+            and out * inn >= _WGRAD_TN_MIN_WEIGHT)
+
+
 def _wgrad_mode(dy2, x2):
     """_C.wgrad_tn mode for this wgrad; 0 = plain addmm on the operands
     as they are."""
-    if _C is None or os.environ.get("FMS_AMD_WGRAD") == "nt":
-        return 0
     if not (dy2.is_cuda and x2.is_cuda and dy2.dtype == torch.bfloat16
             and x2.dtype == torch.bfloat16):
         return 0
-    tokens, out = dy2.shape
-    inn = x2.shape[1]
-    if tokens % 8 or out % 8 or inn % 8:
+    if not _wgrad_tn_shape(dy2.shape[0], dy2.shape[1], x2.shape[1]):
         return 0
-    if tokens < _WGRAD_TN_MIN_TOKENS or out * inn < _WGRAD_TN_MIN_WEIGHT:
+    if not (_transpose_reads(dy2) and _transpose_reads(x2)):
         return 0
-    for t in (dy2, x2):     # what transpose.hip reads without a copy
-        if (t.stride(1) != 1 or t.stride(0) % 8 or t.stride(0) < t.shape[1]
-                or t.data_ptr() % 16):
-            return 0
     return 3
+
+
+def _dgrad_tn_shape(tokens, out, inn):
+    """The part of _dgrad_mode's rule that the shape decides."""
+    if _C is None or os.environ.get("FMS_AMD_DGRAD") == "nn":
+        return False
+    if out % 8 or inn % 8:
+        return False
+    return (tokens >= _DGRAD_TN_MIN_TOKENS
+            and out * inn >= _DGRAD_TN_MIN_WEIGHT)
 
 
 def _dgrad_mode(dy2, w):
     """True where the dgrad dx = dy2 @ w goes through _C.dgrad_tn; False =
     the plain matmul on the operands as they are."""
-    if _C is None or os.environ.get("FMS_AMD_DGRAD") == "nn":
-        return False
     if not (dy2.is_cuda and w.is_cuda and dy2.dtype == torch.bfloat16
             and w.dtype == torch.bfloat16 and dy2.dim() == 2 and w.dim() == 2):
         return False
     tokens, out = dy2.shape
-    inn = w.shape[1]
-    if out != w.shape[0] or out % 8 or inn % 8:
-        return False
-    if tokens < _DGRAD_TN_MIN_TOKENS or out * inn < _DGRAD_TN_MIN_WEIGHT:
+    if out != w.shape[0] or not _dgrad_tn_shape(tokens, out, w.shape[1]):
         return False
     if dy2.stride(1) != 1 or dy2.stride(0) < out:   # the GEMM reads it as is
         return False
-    # what transpose.hip reads without a copy
-    return not (w.stride(1) != 1 or w.stride(0) % 8 or w.stride(0) < inn
-                or w.data_ptr() % 16)
+    return _transpose_reads(w)
 
 
 class _DirectWgradLinearFn(torch.autograd.Function):
@@ -830,6 +851,101 @@ def swiglu(gu):
             return _SwiGLUFn.apply(gu.bfloat16()).half()
         return _SwiGLUFn.apply(gu)
     return reference.swiglu(gu)
+
+
+# --------------------------------------------------------------------------
+# The SwiGLU MLP, y = swiglu(x @ wg1^T) @ w2^T (+ residual), as one
+# autograd function (see the comment block above _DirectWgradLinearFn)
+# --------------------------------------------------------------------------
+def _mlp_bwd_fused(x2, wg1, w2):
+    """True where the backward of the MLP on x2 (tokens, emb) takes the
+    fused route: both weights attached to a flat grad buffer, and both
+    wgrads and both dgrads on their TN routes. The shapes decide for the
+    operands the function makes itself (gu, dh, dgu: contiguous, from the
+    allocator); dy is made contiguous in the backward if it is not."""
+    if os.environ.get("FMS_AMD_MLP_BWD") == "split":
+        return False
+    if not (_direct_wgrad_on(wg1) and _direct_wgrad_on(w2)):
+        return False
+    if not (x2.is_cuda and all(t.dtype == torch.bfloat16 and t.dim() == 2
+                               for t in (x2, wg1, w2))):
+        return False
+    tokens, emb = x2.shape
+    hid2, hid = wg1.shape[0], w2.shape[1]
+    if wg1.shape[1] != emb or w2.shape[0] != emb or hid2 != 2 * hid:
+        return False
+    if not (_wgrad_tn_shape(tokens, hid2, emb)
+            and _wgrad_tn_shape(tokens, emb, hid)
+            and _dgrad_tn_shape(tokens, hid2, emb)
+            and _dgrad_tn_shape(tokens, emb, hid)):
+        return False
+    return all(_transpose_reads(t) for t in (x2, wg1, w2))
+
+
+class _SwiGLUMLPFn(torch.autograd.Function):
+    """The forward is linear_flat -> swiglu -> linear_flat call for call,
+    but saves gu alone: the backward's one pass over dh and gu
+    (_C.swiglu_bwd_t) recomputes h, and emits it and dgu transposed for the
+    wgrads. The flat-grad protocol is _DirectWgradLinearFn's, per weight."""
+
+    @staticmethod
+    def forward(ctx, x, wg1, w2, residual):
+        # attribute holders stashed at forward time: saved_tensors can
+        # return attr-less re-wrapped tensors (e.g. under AC recompute)
+        ctx.targets = [(w._flat_grad_view, w, getattr(w, "_wgrad_done", None))
+                       for w in (wg1, w2)]
+        ctx.res_shape = residual.shape if residual is not None else None
+        x2 = x.reshape(-1, x.shape[-1])
+        gu = x2 @ wg1.t()
+        h = _C.swiglu_fwd(gu)
+        if residual is not None:
+            y = torch.addmm(residual.reshape(x2.shape[0], -1), h, w2.t())
+        else:
+            y = h @ w2.t()
+        ctx.save_for_backward(x, gu, wg1, w2)
+        return y.view(*x.shape[:-1], w2.shape[0])
+
+    @staticmethod
+    def _wgrad(target, dy, x, dy_pre):
+        """One weight's grad into its flat grad view: first touch since
+        zero_grad overwrites, later touches accumulate."""
+        gview, wobj, cb = target
+        fresh = getattr(wobj, "_wgrad_fresh", False)
+        _C.wgrad_tn_pre(dy, x, gview, not fresh, dy_pre, not dy_pre)
+        if fresh:
+            wobj._wgrad_fresh = False
+        if cb is not None:
+            cb()
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gu, wg1, w2 = ctx.saved_tensors
+        dy2 = dy.reshape(-1, dy.shape[-1])
+        if not _transpose_reads(dy2):
+            dy2 = dy2.contiguous()
+        dh = _C.dgrad_tn(dy2, w2)
+        dgu, dguT, hT = _C.swiglu_bwd_t(dh, gu)
+        del dh
+        _SwiGLUMLPFn._wgrad(ctx.targets[1], dy2, hT, False)     # down
+        del hT
+        _SwiGLUMLPFn._wgrad(ctx.targets[0], dguT,               # gate|up
+                            x.reshape(-1, x.shape[-1]), True)
+        del dguT
+        dx = (_C.dgrad_tn(dgu, wg1).view(x.shape)
+              if ctx.needs_input_grad[0] else None)
+        dres = dy.reshape(ctx.res_shape) if ctx.res_shape is not None else None
+        return dx, None, None, dres
+
+
+def swiglu_mlp(x, wg1, w2, residual=None):
+    """swiglu(x @ wg1^T) @ w2^T (+ residual), wg1 the fused gate|up weight
+    (2H, emb) and w2 the down weight (emb, H). Where _mlp_bwd_fused holds
+    it is one autograd function with a fused backward; everywhere else
+    (plain models, frozen weights, small shapes, CPU, FMS_AMD_WGRAD=nt,
+    FMS_AMD_DGRAD=nn, FMS_AMD_MLP_BWD=split) the composition below."""
+    if _mlp_bwd_fused(x.reshape(-1, x.shape[-1]), wg1, w2):
+        return _SwiGLUMLPFn.apply(x, wg1, w2, residual)
+    return linear_flat(swiglu(linear_flat(x, wg1)), w2, residual)
 
 
 # --------------------------------------------------------------------------

@@ -31,6 +31,8 @@ void launch_rope(const void*, void*, const float*, const float*, int, int,
 void launch_swiglu_fwd(const void*, void*, long long, int, hipStream_t);
 void launch_swiglu_bwd(const void*, const void*, void*, long long, int,
                        hipStream_t);
+void launch_swiglu_bwd_t(const void*, const void*, void*, void*, void*,
+                         long long, int, hipStream_t);
 void launch_transpose_bf16(const void*, void*, long long, long long,
                            long long, hipStream_t);
 void launch_ce_fwd_bwd(void*, const long long*, float*, const float*,
@@ -313,6 +315,36 @@ Tensor swiglu_bwd(Tensor dy, Tensor gu) {
   return dgu;
 }
 
+// swiglu_bwd plus the two transposes the MLP's wgrads need, in one pass
+// (swiglu.hip, swiglu_bwd_t_kernel): dh (rows, H), gu (rows, 2H) ->
+// (dgu (rows, 2H), dguT (2H, rows) = dgu^T, hT (H, rows) = swiglu_fwd(gu)^T),
+// each with the bits swiglu_bwd, swiglu_fwd and transpose_bf16 give.
+std::tuple<Tensor, Tensor, Tensor> swiglu_bwd_t(Tensor dh, Tensor gu) {
+  CHECK_BF16_CONTIG(dh);
+  CHECK_BF16_CONTIG(gu);
+  TORCH_CHECK(dh.is_cuda() && gu.is_cuda() && dh.device() == gu.device(),
+              "swiglu_bwd_t: dh and gu must be on one GPU");
+  TORCH_CHECK(dh.dim() == 2 && gu.dim() == 2 && gu.size(0) == dh.size(0) &&
+                  gu.size(1) == 2 * dh.size(1),
+              "swiglu_bwd_t: dh (rows, H) and gu (rows, 2H) expected");
+  const long long rows = dh.size(0), H = dh.size(1);
+  TORCH_CHECK(rows > 0 && H > 0 && rows % 8 == 0 && H % 8 == 0,
+              "swiglu_bwd_t: rows % 8 == 0 and H % 8 == 0 expected");
+  TORCH_CHECK(H < (1LL << 30) &&
+                  (rows + 63) / 64 * ((H + 63) / 64) < (1LL << 31),
+              "swiglu_bwd_t: too many tiles for one grid");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dh.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(gu.data_ptr()) % 16 == 0,
+              "swiglu_bwd_t: dh and gu must be 16-byte aligned");
+  auto dgu = torch::empty_like(gu);
+  auto dguT = torch::empty({2 * H, rows}, gu.options());
+  auto hT = torch::empty({H, rows}, gu.options());
+  launch_swiglu_bwd_t(dh.data_ptr(), gu.data_ptr(), dgu.data_ptr(),
+                      dguT.data_ptr(), hT.data_ptr(), rows, (int)H,
+                      cur_stream());
+  return {dgu, dguT, hT};
+}
+
 // src (rows, cols) bf16 with unit column stride and a row stride >= cols
 // (a column slice of a wider buffer qualifies) -> contiguous (cols, rows).
 static bool transpose_src_ok(const Tensor& t) {
@@ -374,7 +406,36 @@ void wgrad_tn(Tensor dy2, Tensor x2, Tensor gview, bool accumulate,
   ++wgrad_tn_count;
 }
 
-// Calls of wgrad_tn so far: lets a test see which route a backward took.
+// wgrad_tn mode 3 for a caller that already holds an operand transposed
+// (swiglu_bwd_t's dguT and hT): with dy_pre, `dy` is dy2^T (out, tokens)
+// contiguous, with x_pre `x` is x2^T (in, tokens) contiguous; an operand
+// given as it is, (tokens, .), is transposed here as wgrad_tn does. The
+// GEMM is wgrad_tn's mode-3 call on operands with the same bits.
+void wgrad_tn_pre(Tensor dy, Tensor x, Tensor gview, bool accumulate,
+                  bool dy_pre, bool x_pre) {
+  for (const Tensor* t : {&dy, &x})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16 &&
+                    t->dim() == 2 && t->device() == gview.device(),
+                "wgrad_tn_pre: operands must be 2-D bf16 tensors on gview's "
+                "GPU");
+  TORCH_CHECK((!dy_pre || dy.is_contiguous()) && (!x_pre || x.is_contiguous()),
+              "wgrad_tn_pre: an operand given transposed must be contiguous");
+  const int64_t tokens = dy.size(dy_pre ? 1 : 0);
+  TORCH_CHECK(x.size(x_pre ? 1 : 0) == tokens && tokens % 8 == 0,
+              "wgrad_tn_pre: both operands must have the same tokens, a "
+              "multiple of 8");
+  TORCH_CHECK(gview.scalar_type() == torch::kBFloat16 && gview.dim() == 2 &&
+                  gview.size(0) == dy.size(dy_pre ? 0 : 1) &&
+                  gview.size(1) == x.size(x_pre ? 0 : 1),
+              "wgrad_tn_pre: gview must be bf16 (out, in)");
+  Tensor a = dy_pre ? dy : transpose_bf16(dy, c10::nullopt);
+  Tensor b = x_pre ? x : transpose_bf16(x, c10::nullopt);
+  at::addmm_out(gview, gview, a, b.t(), accumulate ? 1 : 0, 1);
+  ++wgrad_tn_count;
+}
+
+// Calls of wgrad_tn and wgrad_tn_pre so far: lets a test see which route
+// a backward took.
 int64_t wgrad_tn_calls() { return wgrad_tn_count; }
 
 // dx = dy2 @ w for dy2 (tokens, out) and a weight w (out, in). As it
@@ -1595,9 +1656,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("rope_into", &rope_into);
   mod.def("swiglu_fwd", &swiglu_fwd);
   mod.def("swiglu_bwd", &swiglu_bwd);
+  mod.def("swiglu_bwd_t", &swiglu_bwd_t);
   mod.def("transpose_bf16", &transpose_bf16, pybind11::arg("src"),
           pybind11::arg("out") = pybind11::none());
   mod.def("wgrad_tn", &wgrad_tn);
+  mod.def("wgrad_tn_pre", &wgrad_tn_pre);
   mod.def("wgrad_tn_calls", &wgrad_tn_calls);
   mod.def("dgrad_tn", &dgrad_tn);
   mod.def("dgrad_tn_calls", &dgrad_tn_calls);

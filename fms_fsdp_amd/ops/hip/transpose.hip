@@ -6,24 +6,8 @@
 // along a row, of the source on the way in and of the destination on the
 // way out, and the 2-byte element shuffle happens in a 64x64 LDS tile.
 //
-// LDS image: row-major [64][64] bf16 (128-B rows = 8 chunks of 16 B), the
-// chunk index XOR-ed with (row / 8) % 8.
-//   fill  ds_write_b128, 8 consecutive lanes = one tile row: they cover
-//         the row's 128 B whatever the chunk permutation, conflict-free.
-//   drain 8 ds_read_u16 per lane (banked by dword mod 32, per 32-lane
-//         half). A half holds 8 lanes per destination row, lane k reading
-//         tile rows 8k..8k+7 at one column, and 4 destination rows
-//         (columns c..c+3 of one chunk). Unswizzled, the 8 row groups sit
-//         on the same 2 banks (rows are 32 dwords: 8-way); with the XOR
-//         group k reads chunk (c/8)^k, 8 distinct 4-bank slots, and the 4
-//         columns share 2 dwords of a slot: conflict-free.
-// Per tile that is 8 ds_write_b128 + 64 ds_read_u16 wave-instructions,
-// about 230 LDS cycles against the ~2200 clocks a CU's share of HBM needs
-// for the tile's 16 KB.
-#include "common.h"
-
-#define TR_TILE 64
-#define TR_CHUNKS (TR_TILE / 8)
+// The tile, its swizzle and the bank arithmetic are in transpose_tile.h.
+#include "transpose_tile.h"
 
 // vec_dst: rows % 8 == 0, so every 8-element run of a destination row is
 // 16-B aligned. Otherwise the drain stores element-wise (correct for any
@@ -48,20 +32,16 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(
     bf16x8 v = {};
     if (r < rows && c < cols)   // cols % 8 == 0: a chunk is all in or out
       v = *(const bf16x8*)(src + r * src_stride + c);
-    tile[lr * TR_CHUNKS + (sub ^ ((lr >> 3) & 7))] = v;
+    tr_tile_put(tile, lr, sub, v);
   }
   __syncthreads();
 
-  const short* ts = (const short*)tile;
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
     const int lc = line + p * 32;            // tile column = dst row
     const long long c = c0 + lc, r = r0 + sub * 8;
     if (c >= cols || r >= rows) continue;
-    const int col = ((((lc >> 3) ^ sub) & 7) << 3) + (lc & 7);
-    bf16x8 o;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o.v[i] = ts[(sub * 8 + i) * TR_TILE + col];
+    const bf16x8 o = tr_tile_take(tile, lc, sub);
     short* d = dst + c * rows + r;
     if (vec_dst) {   // rows % 8 == 0 and r % 8 == 0: the run is all inside
       *(bf16x8*)d = o;

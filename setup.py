@@ -30,7 +30,7 @@ HIP_EXTRA_FLAGS = {"ssd_diag.hip": NO_PACKED_FP32,
                    "ssd_diag_bwd.hip": NO_PACKED_FP32}
 # headers the .hip sources include: a newer header rebuilds every object
 HIP_HEADERS = ["common.h", "attn_sched.h", "attn_ws.h", "attn_frag.h",
-               "attn_decode_plan.h", "ssd_diag_frag.h"]
+               "attn_decode_plan.h", "ssd_diag_frag.h", "transpose_tile.h"]
 
 
 def compile_hip_objects():
