@@ -121,3 +121,8 @@ class train_config:
     # the two-pass kernel of ops/hip/ssd_diag_bwd.hip. Applied once at
     # start-up through ops.ssd_diag_backward().
     ssd_diag_bwd: str = "gemm"
+    # Inter-chunk state chain of the Mamba2 scan: "gemm" is the states
+    # einsum, the (nc x nc) decay matrix and the prev einsum, "fused" runs
+    # the kernels of ops/hip/ssd_state.hip. Applied once at start-up
+    # through ops.ssd_state_chain().
+    ssd_state_chain: str = "gemm"

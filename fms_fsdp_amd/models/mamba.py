@@ -93,7 +93,7 @@ def _doc_rel_start(doc_start, chunk):
 
 
 def ssd_chunked(x, dt, A, B, C, chunk, doc_start=None,
-                return_final_state=False):
+                return_final_state=False, initial_state=None):
     """State-space dual scan (fp32 math).
 
     x (b,l,h,p), dt (b,l,h) [already softplus'ed], A (h) [negative],
@@ -111,7 +111,14 @@ def ssd_chunked(x, dt, A, B, C, chunk, doc_start=None,
     return_final_state: also return the state after the last token, fp32
     (b, h, p, n): the row of the inter-chunk matrix the scan itself never
     needs (the decay of every chunk's state to the end of the sequence).
+
+    initial_state: fp32 (b, h, p, n) state in front of the first token
+    (None = zero); it reaches every chunk through the decay from the start
+    of the sequence. It does not combine with doc_start.
     """
+    if initial_state is not None and doc_start is not None:
+        raise ValueError("ssd_chunked: initial_state and doc_start do not "
+                         "combine")
     b, l, h, p = x.shape
     g, n = B.shape[2], B.shape[3]
     assert l % chunk == 0, f"seq len {l} must divide chunk {chunk}"
@@ -185,6 +192,13 @@ def ssd_chunked(x, dt, A, B, C, chunk, doc_start=None,
     # shift the tiny decay matrix, not the big states tensor
     Wsh = torch.cat([torch.zeros_like(W[:, :, :1]), W[:, :, :-1]], dim=2)
     prev_states = torch.einsum("bhzc,bchnp->bzhnp", Wsh, states)  # (b,nc,h,n,p)
+    if initial_state is not None:
+        # decay from the start of the sequence to the start of chunk z / to
+        # the end of the sequence
+        h0 = initial_state.float().transpose(-1, -2)            # (b,h,n,p)
+        Gcs = G.cumsum(-1)                                      # (b,h,nc)
+        prev_states = prev_states + torch.einsum(
+            "bhz,bhnp->bzhnp", torch.exp(Gcs - G), h0)
 
     # off-diagonal: Y_off[i] = C_i exp(dA_cs[i]) S_{c-1} — C stays per
     # group; the per-(q,h) decay multiplies the GEMM OUTPUT (size h*p)
@@ -201,6 +215,8 @@ def ssd_chunked(x, dt, A, B, C, chunk, doc_start=None,
     y = (y_diag + y_off).reshape(b, l, h, p)
     if return_final_state:
         final = torch.einsum("bhc,bchnp->bhnp", W[:, :, -1], states.float())
+        if initial_state is not None:
+            final = final + torch.exp(Gcs[..., -1])[..., None, None] * h0
         return y, final.permute(0, 1, 3, 2).contiguous()
     return y
 
@@ -251,7 +267,8 @@ class Mamba2Mixer(nn.Module):
         self.norm.reset_parameters()
 
     def _scan_fused(self, b, l, x, dt, z, B, C, dtb, Alog, D_,
-                    doc_start=None, doc_end=None, return_final_state=False):
+                    doc_start=None, doc_end=None, return_final_state=False,
+                    initial_state=None):
         """GPU SSD scan: the elementwise chains run as fused HIP kernels
         (ops/hip/ssd.hip — prep/xdt/ygate, each with a custom backward),
         the intra-chunk term y_diag as the fused MFMA kernel of
@@ -264,7 +281,12 @@ class Mamba2Mixer(nn.Module):
         document start: masked xdt / y_diag / ygate kernels plus a
         select on the inter-chunk matrix (see ssd_chunked).
         return_final_state: also the fp32 (b, h, p, n) state after the last
-        token (see ssd_chunked)."""
+        token (see ssd_chunked).
+        initial_state: fp32 (b, h, p, n) state in front of the first token.
+        With it, or under ops.ssd_state_chain("fused"), the inter-chunk
+        chain runs as the kernels of ops/hip/ssd_state.hip (chunk states,
+        then the sequential state pass) instead of the closed form below,
+        which can only start from zero."""
         doc_mask = None if doc_start is None else ops.DocMask(doc_start,
                                                               doc_end)
         h, p = self.nheads, self.headdim
@@ -288,6 +310,47 @@ class Mamba2Mixer(nn.Module):
         y_diag = ops.ssd_diag(C.reshape(b * l, g * n), B.reshape(b * l, g * n),
                               dacs, xdt, h, g, p, n, Q,
                               doc_mask=doc_mask)           # (N, Q, p) bf16
+        if initial_state is not None or ops.ssd_state_chain() == "fused":
+            prev, final = self._state_chain_fused(
+                b, B, xdtd, dacs, doc_mask, initial_state, return_final_state)
+        else:
+            prev, final = self._state_chain_gemm(
+                b, nc, Bm, xdtd, dacs, doc_start, return_final_state)
+        # output ordering "bcgqrp" = the bmm-natural layout; the ygate
+        # kernel reads it in place
+        y_off = torch.einsum(
+            "bcqgn,bcgrnp->bcgqrp", Cm,
+            prev.view(b, nc, g, rep, n, p))
+        out = ops.ssd_ygate(
+            y_diag.reshape(b * l, h * p),
+            y_off.contiguous().view(b * l, h * p),
+            dacs, x2, D_, z2, h, g, p, Q, doc_mask=doc_mask)
+        if return_final_state:
+            return out.view(b, l, h * p), final
+        return out.view(b, l, h * p)
+
+    def _state_chain_fused(self, b, B, xdtd, dacs, doc_mask, initial_state,
+                           want_final):
+        """(prev, final) of the inter-chunk chain from the kernels of
+        ops/hip/ssd_state.hip: chunk states, then the sequential state
+        pass from initial_state (None = zero)."""
+        h, p, g, n, Q = (self.nheads, self.headdim, self.ngroups,
+                         self.d_state, self.chunk)
+        states = ops.ssd_chunk_state(B.reshape(-1, g * n), xdtd, h, g, p, n,
+                                     Q)                    # (b*nc*h, n, p)
+        out = ops.ssd_state_pass(states, dacs, b, h, p, n, Q,
+                                 doc_mask=doc_mask,
+                                 initial_state=initial_state,
+                                 return_final_state=want_final)
+        return out if want_final else (out, None)
+
+    def _state_chain_gemm(self, b, nc, Bm, xdtd, dacs, doc_start, want_final):
+        """(prev, final) of the inter-chunk chain in closed form, from a
+        zero state: two hipBLASLt einsums around the (nc x nc) decay
+        matrix."""
+        h, p, g, n, Q = (self.nheads, self.headdim, self.ngroups,
+                         self.d_state, self.chunk)
+        rep = h // g
         # the whole inter-chunk state chain runs bf16 (W entries are
         # decays in [0,1], states are sums of bf16-rounded products with
         # fp32 GEMM accumulation) — halves the traffic of the biggest
@@ -306,21 +369,10 @@ class Mamba2Mixer(nn.Module):
         Wsh = torch.cat([torch.zeros_like(W[:, :, :1]), W[:, :, :-1]],
                         dim=2).to(torch.bfloat16)
         prev = torch.einsum("bhzc,bchnp->bzhnp", Wsh, states)
-        # output ordering "bcgqrp" = the bmm-natural layout; the ygate
-        # kernel reads it in place
-        y_off = torch.einsum(
-            "bcqgn,bcgrnp->bcgqrp", Cm,
-            prev.view(b, nc, g, rep, n, p))
-        out = ops.ssd_ygate(
-            y_diag.reshape(b * l, h * p),
-            y_off.contiguous().view(b * l, h * p),
-            dacs, x2, D_, z2, h, g, p, Q, doc_mask=doc_mask)
-        if return_final_state:
-            final = torch.einsum("bhc,bchnp->bhnp", W[:, :, -1],
-                                 states.float())
-            return out.view(b, l, h * p), \
-                final.permute(0, 1, 3, 2).contiguous()
-        return out.view(b, l, h * p)
+        if not want_final:
+            return prev, None
+        final = torch.einsum("bhc,bchnp->bhnp", W[:, :, -1], states.float())
+        return prev, final.permute(0, 1, 3, 2).contiguous()
 
     def _fused_scan_ok(self, u):
         return u.is_cuda and u.dtype == torch.bfloat16 \
@@ -329,12 +381,15 @@ class Mamba2Mixer(nn.Module):
 
     def _forward_cached(self, u, cache):
         """l new tokens over an ops.MambaCache (inference only). in_proj
-        and the conv run once over all l tokens. On a fresh cache the
-        first l // chunk * chunk tokens take the chunked scan, which hands
-        its final state to the cache; the remaining l % chunk tokens, and
-        every token on a cache already in use (the single decode token as
-        a rule), step the recurrence from the cached state with
-        ops.ssd_state_update."""
+        and the conv run once over all l tokens. The first l // chunk *
+        chunk tokens take the chunked scan, from zero on a fresh cache and
+        from cache.ssm on one in use, and hand its final state to the
+        cache; the remaining l % chunk tokens (the single decode token as
+        a rule) step the recurrence from the cached state with
+        ops.ssd_state_update. FMS_AMD_MAMBA_PREFILL=step sends every token
+        on a cache in use through the step kernel instead, as does a head
+        geometry the state-pass kernel does not serve
+        (ops.ssd_state_pass_has_kernel)."""
         if torch.is_grad_enabled() and (
                 u.requires_grad or self.in_proj.weight.requires_grad):
             raise RuntimeError(
@@ -359,13 +414,19 @@ class Mamba2Mixer(nn.Module):
         x, B, C = torch.split(xBC, [self.d_inner, g * n, g * n], dim=-1)
 
         outs = []
-        m = l // Q * Q if fresh else 0
+        # on a cache in use the GPU scan needs the state-pass kernel
+        chunked = fresh or (
+            os.environ.get("FMS_AMD_MAMBA_PREFILL") != "step"
+            and (not self._fused_scan_ok(u)
+                 or ops.ssd_state_pass_has_kernel(n, p)))
+        m = l // Q * Q if chunked else 0
         if m:
+            init = None if fresh else cache.ssm
             xm, dtm, zm, Bm, Cm = (t[:, :m] for t in (x, dt, z, B, C))
             if self._fused_scan_ok(u):
                 y, final = self._scan_fused(
                     b, m, xm, dtm, zm, Bm, Cm, self.dt_bias, self.A_log,
-                    self.D, return_final_state=True)
+                    self.D, return_final_state=True, initial_state=init)
             else:
                 dtf = F.softplus(dtm.float() + self.dt_bias.float())
                 xh = xm.reshape(b, m, h, p).float()
@@ -373,7 +434,7 @@ class Mamba2Mixer(nn.Module):
                     xh, dtf, -torch.exp(self.A_log.float()),
                     Bm.reshape(b, m, g, n).float(),
                     Cm.reshape(b, m, g, n).float(), Q,
-                    return_final_state=True)
+                    return_final_state=True, initial_state=init)
                 y = y + xh * self.D.view(1, 1, -1, 1)
                 y = y.reshape(b, m, self.d_inner).to(u.dtype) * F.silu(zm)
             cache.ssm.copy_(final)

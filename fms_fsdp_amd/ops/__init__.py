@@ -1438,6 +1438,169 @@ def ssd_diag(C2d, B2d, dacs, xdt, H, G, P, N, Q, doc_mask=None):
                             xdt.contiguous(), H, G, P, N, Q, doc_mask)
 
 
+# --------------------------------------------------------------------------
+# Inter-chunk state chain (ops/hip/ssd_state.hip): the chunk states as an
+# MFMA kernel, the chunk-to-chunk recurrence as a sequential scan that
+# starts from any state.
+# --------------------------------------------------------------------------
+_SSD_STATE_MODES = ("gemm", "fused")
+_ssd_state_mode = None
+
+
+def ssd_state_chain(mode=None):
+    """Get/set the process-wide inter-chunk state chain of the fused scan
+    (Mamba2Mixer._scan_fused): "gemm" (default) is the states einsum, the
+    (nc x nc) decay matrix and the prev einsum; "fused" runs the kernels
+    of ops/hip/ssd_state.hip. A scan from an initial state on the GPU takes
+    the kernels whatever the mode. None = query. Returns the previous mode;
+    until it is set, FMS_AMD_SSD_STATE gives the mode."""
+    global _ssd_state_mode
+    prev = _ssd_state_mode
+    if prev is None:
+        prev = os.environ.get("FMS_AMD_SSD_STATE") or "gemm"
+        if prev not in _SSD_STATE_MODES:
+            raise ValueError(f"FMS_AMD_SSD_STATE must be one of "
+                             f"{_SSD_STATE_MODES}, got {prev!r}")
+    if mode is not None:
+        if mode not in _SSD_STATE_MODES:
+            raise ValueError(f"ssd_state_chain: mode must be one of "
+                             f"{_SSD_STATE_MODES}, got {mode!r}")
+        _ssd_state_mode = mode
+    return prev
+
+
+def _ssd_chunk_state_gemm(B2d, xdtd, H, G, P, N, Q):
+    bc = B2d.shape[0] // Q
+    return torch.einsum(
+        "ckgn,cgrkp->cgrnp", B2d.reshape(bc, Q, G, N),
+        xdtd.reshape(bc, G, H // G, Q, P)).reshape(bc * H, N, P)
+
+
+class _SSDChunkStateFn(torch.autograd.Function):
+    """states (bc*H, N, P) from ssd_chunk_state_kernel. The backward is the
+    pair of einsums autograd runs for the states einsum: dxdtd from B and
+    dS, dB from xdtd and dS summed over the heads of a group."""
+
+    @staticmethod
+    def forward(ctx, B2d, xdtd, H, G, P, N, Q):
+        ext = _require_ext("ssd_chunk_state")
+        S = ext.ssd_chunk_state(B2d, xdtd, H, G, P, N, Q)
+        ctx.save_for_backward(B2d, xdtd)
+        ctx.meta = (H, G, P, N, Q)
+        return S
+
+    @staticmethod
+    def backward(ctx, dS):
+        B2d, xdtd = ctx.saved_tensors
+        H, G, P, N, Q = ctx.meta
+        bc = B2d.shape[0] // Q
+        rep = H // G
+        dS5 = dS.reshape(bc, G, rep, N, P)
+        dxdtd = torch.einsum("ckgn,cgrnp->cgrkp", B2d.reshape(bc, Q, G, N),
+                             dS5)
+        dB = torch.einsum("cgrkp,cgrnp->ckgn",
+                          xdtd.view(bc, G, rep, Q, P), dS5)
+        return (dB.reshape(bc * Q, G * N), dxdtd.reshape(xdtd.shape),
+                None, None, None, None, None)
+
+
+def ssd_chunk_state(B2d, xdtd, H, G, P, N, Q):
+    """Chunk states (b*l/Q*H, N, P): S[m] = B_chunk^T xdtd[m]
+    (reference.ssd_chunk_state has the definition). B2d (b*l, G*N) may be a
+    last-dim slice of the conv output; xdtd h-major bf16 from ssd_xdt. On
+    the GPU the bf16 shapes ssd_diag serves run ssd_chunk_state_kernel;
+    CPU tensors, other dtypes and other shapes take the einsum."""
+    if xdtd.is_cuda and xdtd.dtype == torch.bfloat16 \
+            and B2d.dtype == torch.bfloat16 \
+            and _require_ext("ssd_chunk_state").ssd_chunk_state_has_kernel(
+                N, P, Q):
+        return _SSDChunkStateFn.apply(_ssd_diag_view(B2d), xdtd.contiguous(),
+                                      H, G, P, N, Q)
+    return _ssd_chunk_state_gemm(B2d, xdtd, H, G, P, N, Q)
+
+
+class _SSDStatePassFn(torch.autograd.Function):
+    """prev (b*nc*H, N, P) bf16 and the fp32 final state from
+    ssd_state_pass_fwd_kernel; the backward is the reverse scan of
+    ssd_state_pass_bwd_kernel over the saved bf16 prev. Its per-block
+    partials of dG_c are summed here and land in column Q-1 of ddacs."""
+
+    @staticmethod
+    def forward(ctx, states, dacs, initial_state, b, H, P, N, Q, want_final,
+                doc_start=None):
+        ext = _require_ext("ssd_state_pass")
+        nc = states.shape[0] // (b * H)
+        init = None if initial_state is None \
+            else initial_state.detach().float().contiguous()
+        if doc_start is None:
+            out = ext.ssd_state_pass_fwd(states, dacs, b, nc, H, P, N, Q,
+                                         init, want_final)
+            ctx.save_for_backward(out[0], dacs)
+        else:
+            out = ext.ssd_state_pass_fwd_doc(
+                states, dacs, b, nc, H, P, N, Q, init, want_final, doc_start,
+                doc_start.shape[-1])
+            ctx.save_for_backward(out[0], dacs, doc_start)
+        ctx.meta = (b, nc, H, P, N, Q,
+                    None if initial_state is None else initial_state.dtype)
+        if not want_final:
+            return out[0], None
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, dprev, dfinal):
+        prev, dacs, *doc = ctx.saved_tensors
+        b, nc, H, P, N, Q, idt = ctx.meta
+        want_dinit = idt is not None and ctx.needs_input_grad[2]
+        dprev = torch.zeros_like(prev) if dprev is None \
+            else dprev.contiguous().to(prev.dtype)
+        if dfinal is not None:
+            dfinal = dfinal.float().contiguous()
+        if doc:
+            out = _C.ssd_state_pass_bwd_doc(
+                dprev, dfinal, prev, dacs, b, nc, H, P, N, Q, want_dinit,
+                doc[0], doc[0].shape[-1])
+        else:
+            out = _C.ssd_state_pass_bwd(dprev, dfinal, prev, dacs, b, nc, H,
+                                        P, N, Q, want_dinit)
+        ddacs = torch.zeros_like(dacs)
+        ddacs[:, -1] = out[1].sum(0).reshape(-1)
+        dinit = out[2].to(idt) if want_dinit else None
+        return (out[0], ddacs, dinit) + (None,) * 7
+
+
+def ssd_state_pass_has_kernel(N, P):
+    """Whether the state-pass kernels serve (d_state, headdim): P a
+    multiple of 8 and N*P of 512."""
+    return _require_ext("ssd_state_pass").ssd_state_pass_has_kernel(N, P)
+
+
+def ssd_state_pass(states, dacs, b, H, P, N, Q, doc_mask=None,
+                   initial_state=None, return_final_state=False):
+    """The inter-chunk recurrence over the chunk states (b*nc*H, N, P):
+    prev[b, c, h] = the state in front of chunk c, Hc_c = keep_c
+    exp(dacs[m, Q-1]) Hc_{c-1} + states[b, c, h], from initial_state
+    (b, H, P, N) or zero (reference.ssd_state_pass has the definition).
+    Returns prev, with return_final_state also the fp32 (b, H, P, N) state
+    behind the last chunk. Gradients reach states, dacs and initial_state.
+    initial_state and doc_mask do not combine. bf16 states on the GPU run
+    the kernels of ops/hip/ssd_state.hip, and a shape they do not serve
+    (ssd_state_pass_has_kernel) raises; CPU tensors and other dtypes run
+    the oracle."""
+    if doc_mask is not None and initial_state is not None:
+        raise ValueError("ssd_state_pass: initial_state and doc_mask do not "
+                         "combine")
+    if not states.is_cuda or states.dtype != torch.bfloat16:
+        return reference.ssd_state_pass(states, dacs, b, H, P, N, Q,
+                                        doc_mask, initial_state,
+                                        return_final_state)
+    prev, final = _SSDStatePassFn.apply(
+        states.contiguous(), dacs.contiguous(), initial_state, b, H, P, N, Q,
+        return_final_state,
+        *_doc_start_arg(doc_mask, states.shape[0] // H * Q, Q))
+    return (prev, final) if return_final_state else prev
+
+
 class _SSDYGateFn(torch.autograd.Function):
     """out = (ydiag + yoff*exp(dacs) + x*D) * silu(z), bf16 in one pass
     (y assembly + D residual + the gated epilogue)."""

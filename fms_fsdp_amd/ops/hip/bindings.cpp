@@ -119,6 +119,18 @@ void launch_ssd_step(float*, const void*, const void*, const void*,
                      const float*, void*, long long, int, int, int, int, int,
                      long long, long long, long long, long long, long long,
                      hipStream_t);
+int ssd_chunk_state_plan(long long, int, int*);
+void launch_ssd_chunk_state(const void*, const void*, void*, long long, int,
+                            int, int, int, int, long long, int, int,
+                            hipStream_t);
+int ssd_state_pass_block(int, int);
+void launch_ssd_state_pass_fwd(const void*, const float*, const float*, void*,
+                               float*, const int*, long long, int, int, int,
+                               int, int, hipStream_t);
+void launch_ssd_state_pass_bwd(const void*, const float*, const void*,
+                               const float*, void*, float*, float*, const int*,
+                               long long, int, int, int, int, int,
+                               hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -1637,7 +1649,226 @@ Tensor cconv_update(Tensor conv_state, Tensor x, Tensor w, Tensor bias) {
   return y;
 }
 
+// ---- inter-chunk state chain (ssd_state.hip) ----------------------------
+static int64_t ssd_state_count = 0;
+
+// Launches of the three ssd_state.hip kernels so far.
+int64_t ssd_state_calls() { return ssd_state_count; }
+
+// whether ops.ssd_chunk_state may send (N, P, Q) to the kernel
+bool ssd_chunk_state_has_kernel(int64_t N, int64_t P, int64_t Q) {
+  return ssd_diag_has_kernel(N, P, Q);
+}
+
+// S (bc*H, N, P) bf16 = B^T xdtd per (chunk, head). B (b*l, G*N) bf16
+// last-dim slice read in place (the rule of check_diag_slice); xdtd h-major
+// (bc*H, Q, P) bf16 contiguous in any shape with that element order. `out`
+// (optional) receives the result: bf16 contiguous with bc*H*N*P elements.
+Tensor ssd_chunk_state(Tensor B, Tensor xdtd, int64_t H, int64_t G, int64_t P,
+                       int64_t N, int64_t Q, c10::optional<Tensor> out) {
+  const char* op = "ssd_chunk_state";
+  TORCH_CHECK(H > 0 && G > 0 && H % G == 0, op,
+              ": H must be a multiple of G");
+  TORCH_CHECK(N > 0 && P > 0 && N <= 256 && P <= 256 &&
+                  ssd_diag_supported((int)N, (int)P),
+              op, ": no kernel for N = ", N, ", P = ", P);
+  TORCH_CHECK(Q >= 32 && Q <= 256 && Q % 32 == 0, op,
+              ": Q must be a multiple of 32 in [32, 256], got ", Q);
+  TORCH_CHECK(xdtd.is_cuda(), op, ": xdtd must be on a GPU");
+  TORCH_CHECK(B.dim() == 2 && B.size(0) % Q == 0, op,
+              ": B rows must be a multiple of Q");
+  const long long rows = B.size(0);
+  const long long bc = rows / Q;
+  const long long sB = check_diag_slice(B, rows, G * N, xdtd, "B");
+  check_bf16_numel(xdtd, rows * H * P, "xdtd");
+  TORCH_CHECK(aligned16(xdtd), op, ": xdtd must be 16-byte aligned");
+  TORCH_CHECK(sB < (1LL << 31), op, ": row stride of B too large");
+  int HB = 1;
+  const int nhb = ssd_chunk_state_plan(bc * G, (int)(H / G), &HB);
+  TORCH_CHECK(bc * G * nhb < (1LL << 31), op,
+              ": too many chunks for one grid");
+  if (out.has_value()) {
+    check_bf16_numel(*out, bc * H * N * P, "out");
+    TORCH_CHECK(out->device() == xdtd.device() && aligned16(*out), op,
+                ": out must be 16-byte aligned on the GPU of xdtd");
+  }
+  auto S = out.has_value() ? out->view({bc * H, N, P})
+                           : torch::empty({bc * H, N, P}, xdtd.options());
+  if (bc == 0) return S;
+  launch_ssd_chunk_state(B.data_ptr(), xdtd.data_ptr(), S.data_ptr(), bc,
+                         (int)H, (int)G, (int)P, (int)N, (int)Q, sB, HB, nhb,
+                         cur_stream());
+  ++ssd_state_count;
+  return S;
+}
+
+// whether the state-pass kernels serve (N, P): 8 consecutive (k, p) elements
+// per thread inside one state row, whole 64-thread waves per (b, h)
+bool ssd_state_pass_has_kernel(int64_t N, int64_t P) {
+  return P > 0 && N > 0 && P % 8 == 0 && (N * P) % 512 == 0 &&
+         N * P < (1LL << 24);
+}
+
+// shape arguments of the state pass; returns the rows b*nc*H
+static long long check_pass_dims(const char* op, int64_t b, int64_t nc,
+                                 int64_t H, int64_t P, int64_t N, int64_t Q) {
+  TORCH_CHECK(b >= 0 && nc > 0 && H > 0 && Q > 0, op,
+              ": nc, H and Q must be positive and b not negative");
+  TORCH_CHECK(ssd_state_pass_has_kernel(N, P), op, ": P must be a multiple of 8 and N*P of 512, got N = ", N,
+              ", P = ", P);
+  TORCH_CHECK(nc < (1LL << 31) / Q && H < (1LL << 24), op,
+              ": nc*Q and H must fit 32 bits");
+  const int nblk = (int)(N * P / 8) / ssd_state_pass_block((int)N, (int)P);
+  TORCH_CHECK(b * H * nblk < (1LL << 31), op, ": too many rows for one grid");
+  return b * nc * H;
+}
+
+// bf16 contiguous (b*nc*H, N, P) chunk-state tensor on the GPU of dacs
+static void check_pass_states(const char* op, const Tensor& t,
+                              const Tensor& dacs, long long rows, int64_t N,
+                              int64_t P, const char* nm) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dacs.device(), op, ": ", nm,
+              " must be on the GPU of dacs");
+  check_bf16_numel(t, rows * N * P, nm);
+  TORCH_CHECK(aligned16(t), op, ": ", nm, " must be 16-byte aligned");
+}
+
+// fp32 contiguous (b, H, P, N) state (MambaCache.ssm's layout), optional
+static const float* pass_state_ptr(const char* op,
+                                   const c10::optional<Tensor>& t,
+                                   const Tensor& dacs, int64_t b, int64_t H,
+                                   int64_t P, int64_t N, const char* nm) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->scalar_type() == torch::kFloat32 && t->is_contiguous() &&
+                  t->dim() == 4 && t->size(0) == b && t->size(1) == H &&
+                  t->size(2) == P && t->size(3) == N,
+              op, ": ", nm, " must be contiguous fp32 (b, H, P, N)");
+  TORCH_CHECK(t->is_cuda() && t->device() == dacs.device(), op, ": ", nm,
+              " must be on the GPU of dacs");
+  return t->data_ptr<float>();
+}
+
+static const int* pass_doc(const char* op,
+                           const c10::optional<Tensor>& doc_start,
+                           const Tensor& dacs, int64_t b, int64_t nc,
+                           int64_t Q, int64_t l) {
+  const int* ds = doc_ptr(doc_start, b * nc * Q, dacs, "doc_start");
+  if (ds)
+    TORCH_CHECK(doc_nc(b * nc * Q, l, Q) == nc, op,
+                ": row length l must be nc*Q");
+  return ds;
+}
+
+// {prev (b*nc*H, N, P) bf16[, final (b, H, P, N) fp32]}
+static std::vector<Tensor> ssd_state_pass_fwd_impl(
+    Tensor states, Tensor dacs, int64_t b, int64_t nc, int64_t H, int64_t P,
+    int64_t N, int64_t Q, c10::optional<Tensor> initial_state,
+    bool want_final, c10::optional<Tensor> doc_start, int64_t l) {
+  const char* op = "ssd_state_pass_fwd";
+  const long long rows = check_pass_dims(op, b, nc, H, P, N, Q);
+  TORCH_CHECK(dacs.is_cuda(), op, ": dacs must be on a GPU");
+  check_nq(dacs, rows, Q, "dacs");
+  check_pass_states(op, states, dacs, rows, N, P, "states");
+  const float* init =
+      pass_state_ptr(op, initial_state, dacs, b, H, P, N, "initial_state");
+  const int* ds = pass_doc(op, doc_start, dacs, b, nc, Q, l);
+  TORCH_CHECK(!(init && ds), op,
+              ": initial_state and a document mask do not combine");
+  auto prev = torch::empty({rows, N, P}, states.options());
+  std::vector<Tensor> out{prev};
+  float* fin = nullptr;
+  if (want_final) {
+    out.push_back(torch::empty({b, H, P, N}, dacs.options()));
+    fin = out[1].data_ptr<float>();
+  }
+  if (b == 0) return out;
+  launch_ssd_state_pass_fwd(states.data_ptr(), dacs.data_ptr<float>(), init,
+                            prev.data_ptr(), fin, ds, b, (int)nc, (int)H,
+                            (int)P, (int)N, (int)Q, cur_stream());
+  ++ssd_state_count;
+  return out;
+}
+
+std::vector<Tensor> ssd_state_pass_fwd(Tensor states, Tensor dacs, int64_t b,
+                                       int64_t nc, int64_t H, int64_t P,
+                                       int64_t N, int64_t Q,
+                                       c10::optional<Tensor> initial_state,
+                                       bool want_final) {
+  return ssd_state_pass_fwd_impl(states, dacs, b, nc, H, P, N, Q,
+                                 initial_state, want_final, c10::nullopt, 0);
+}
+
+std::vector<Tensor> ssd_state_pass_fwd_doc(
+    Tensor states, Tensor dacs, int64_t b, int64_t nc, int64_t H, int64_t P,
+    int64_t N, int64_t Q, c10::optional<Tensor> initial_state,
+    bool want_final, Tensor doc_start, int64_t l) {
+  return ssd_state_pass_fwd_impl(states, dacs, b, nc, H, P, N, Q,
+                                 initial_state, want_final, doc_start, l);
+}
+
+// {dS (b*nc*H, N, P) bf16, dG partials (blocks, b, nc, H) fp32[, dinitial
+// (b, H, P, N) fp32]}; prev is the forward's saved output
+static std::vector<Tensor> ssd_state_pass_bwd_impl(
+    Tensor dprev, c10::optional<Tensor> dfinal, Tensor prev, Tensor dacs,
+    int64_t b, int64_t nc, int64_t H, int64_t P, int64_t N, int64_t Q,
+    bool want_dinitial, c10::optional<Tensor> doc_start, int64_t l) {
+  const char* op = "ssd_state_pass_bwd";
+  const long long rows = check_pass_dims(op, b, nc, H, P, N, Q);
+  TORCH_CHECK(dacs.is_cuda(), op, ": dacs must be on a GPU");
+  check_nq(dacs, rows, Q, "dacs");
+  check_pass_states(op, dprev, dacs, rows, N, P, "dprev");
+  check_pass_states(op, prev, dacs, rows, N, P, "prev");
+  const float* dfin = pass_state_ptr(op, dfinal, dacs, b, H, P, N, "dfinal");
+  const int* ds = pass_doc(op, doc_start, dacs, b, nc, Q, l);
+  TORCH_CHECK(!(want_dinitial && ds), op,
+              ": initial_state and a document mask do not combine");
+  const int64_t nblk = N * P / 8 / ssd_state_pass_block((int)N, (int)P);
+  std::vector<Tensor> out{
+      torch::empty({rows, N, P}, prev.options()),
+      torch::empty({nblk, b, nc, H}, dacs.options())};
+  float* dinit = nullptr;
+  if (want_dinitial) {
+    out.push_back(torch::empty({b, H, P, N}, dacs.options()));
+    dinit = out[2].data_ptr<float>();
+  }
+  if (b == 0) return out;
+  launch_ssd_state_pass_bwd(dprev.data_ptr(), dfin, prev.data_ptr(),
+                            dacs.data_ptr<float>(), out[0].data_ptr(),
+                            out[1].data_ptr<float>(), dinit, ds, b, (int)nc,
+                            (int)H, (int)P, (int)N, (int)Q, cur_stream());
+  ++ssd_state_count;
+  return out;
+}
+
+std::vector<Tensor> ssd_state_pass_bwd(Tensor dprev,
+                                       c10::optional<Tensor> dfinal,
+                                       Tensor prev, Tensor dacs, int64_t b,
+                                       int64_t nc, int64_t H, int64_t P,
+                                       int64_t N, int64_t Q,
+                                       bool want_dinitial) {
+  return ssd_state_pass_bwd_impl(dprev, dfinal, prev, dacs, b, nc, H, P, N, Q,
+                                 want_dinitial, c10::nullopt, 0);
+}
+
+std::vector<Tensor> ssd_state_pass_bwd_doc(
+    Tensor dprev, c10::optional<Tensor> dfinal, Tensor prev, Tensor dacs,
+    int64_t b, int64_t nc, int64_t H, int64_t P, int64_t N, int64_t Q,
+    bool want_dinitial, Tensor doc_start, int64_t l) {
+  return ssd_state_pass_bwd_impl(dprev, dfinal, prev, dacs, b, nc, H, P, N, Q,
+                                 want_dinitial, doc_start, l);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("ssd_chunk_state", &ssd_chunk_state, py::arg("B"), py::arg("xdtd"),
+          py::arg("H"), py::arg("G"), py::arg("P"), py::arg("N"), py::arg("Q"),
+          py::arg("out") = py::none());
+  mod.def("ssd_chunk_state_has_kernel", &ssd_chunk_state_has_kernel);
+  mod.def("ssd_state_calls", &ssd_state_calls);
+  mod.def("ssd_state_pass_has_kernel", &ssd_state_pass_has_kernel);
+  mod.def("ssd_state_pass_fwd", &ssd_state_pass_fwd);
+  mod.def("ssd_state_pass_fwd_doc", &ssd_state_pass_fwd_doc);
+  mod.def("ssd_state_pass_bwd", &ssd_state_pass_bwd);
+  mod.def("ssd_state_pass_bwd_doc", &ssd_state_pass_bwd_doc);
   mod.def("ssd_step", &ssd_step);
   mod.def("cconv_update", &cconv_update);
   mod.def("segsum_exp_fwd", &segsum_exp_fwd);

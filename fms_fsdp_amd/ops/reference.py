@@ -241,6 +241,59 @@ def ssd_ygate(ydiag, yoff, dacs, x2d, D, z2d, H, G, P, Q, doc_mask=None):
     return (y * zh * torch.sigmoid(zh)).reshape(rows, H * P)
 
 
+def ssd_chunk_state(B2d, xdtd, H, G, P, N, Q):
+    """Chunk states (bc*H, N, P) (oracle of ssd_chunk_state_kernel):
+    S[m, k, p] = sum_q B[bc*Q + q, g*N + k] xdtd[m, q, p], m = bc*H + h,
+    g = h // (H // G). xdtd h-major (bc, H, Q, P) in any shape with that
+    element order."""
+    bc = B2d.shape[0] // Q
+    rep = H // G
+    Bm = B2d.reshape(bc, Q, G, N)
+    xd = xdtd.reshape(bc, G, rep, Q, P)
+    S = torch.einsum("cqgn,cgrqp->cgrnp", Bm, xd)
+    return S.reshape(bc * H, N, P)
+
+
+def ssd_state_pass(states, dacs, b, H, P, N, Q, doc_mask=None,
+                   initial_state=None, return_final_state=False):
+    """The inter-chunk recurrence (oracle of the ssd_state_pass kernels).
+    states (b*nc*H, N, P), dacs (b*nc*H, Q); per (b, h), a_c =
+    exp(dacs[m, Q-1]):
+      Hc_{-1} = initial_state^T (or 0); prev_c = Hc_{c-1}
+      Hc_c = keep_c a_c Hc_{c-1} + S_c
+    keep_c (doc_mask): the document of the chunk's last token began before
+    the chunk, a select to exact 0. initial_state and the final state are
+    (b, H, P, N). Returns prev (b*nc*H, N, P), unrounded, and with
+    return_final_state also Hc_{nc-1} (b, H, P, N)."""
+    if doc_mask is not None and initial_state is not None:
+        raise ValueError("ssd_state_pass: initial_state and doc_mask do not "
+                         "combine")
+    nc = states.shape[0] // (b * H)
+    S = states.reshape(b, nc, H, N, P)
+    ct = torch.promote_types(states.dtype, dacs.dtype)
+    a = torch.exp(dacs.reshape(b, nc, H, Q)[..., -1]).to(ct)     # (b, nc, H)
+    keep = None
+    if doc_mask is not None:
+        keep = doc_rel_start(doc_mask, Q, states.device) \
+            .reshape(b, nc, Q)[..., -1] < 0                      # (b, nc)
+    if initial_state is None:
+        carry = torch.zeros(b, H, N, P, dtype=ct, device=states.device)
+    else:
+        carry = initial_state.to(ct).transpose(-1, -2)
+    prevs = []
+    for c in range(nc):
+        prevs.append(carry)
+        dec = a[:, c, :, None, None] * carry
+        if keep is not None:
+            dec = torch.where(keep[:, c, None, None, None], dec,
+                              torch.zeros_like(dec))
+        carry = dec + S[:, c]
+    prev = torch.stack(prevs, dim=1).reshape(b * nc * H, N, P)
+    if return_final_state:
+        return prev, carry.transpose(-1, -2).contiguous()
+    return prev
+
+
 # --------------------------------------------------------------------------
 # Recurrent decode (ops/hip/ssd_step.hip, cconv_update_kernel): the oracles
 # of _C.ssd_step and _C.cconv_update, same signatures, states updated in

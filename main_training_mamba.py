@@ -41,6 +41,7 @@ def main(**kwargs):
     setup_environ_flags()
     ops.attn_bwd_workspace_limit(cfg.attn_bwd_workspace_mb)
     ops.ssd_diag_backward(cfg.ssd_diag_bwd)
+    ops.ssd_state_chain(cfg.ssd_state_chain)
 
     if rank == 0:
         print(f"--> running with these configs {cfg}")
