@@ -126,3 +126,8 @@ class train_config:
     # the kernels of ops/hip/ssd_state.hip. Applied once at start-up
     # through ops.ssd_state_chain().
     ssd_state_chain: str = "gemm"
+    # Backward of the chunk-state kernel of that chain: "gemm" is the two
+    # einsums autograd runs for the states einsum, "fused" runs the kernel
+    # of ops/hip/ssd_state_bwd.hip. Applied once at start-up through
+    # ops.ssd_chunk_state_backward().
+    ssd_chunk_state_bwd: str = "gemm"

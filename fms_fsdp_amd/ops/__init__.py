@@ -1476,10 +1476,38 @@ def _ssd_chunk_state_gemm(B2d, xdtd, H, G, P, N, Q):
         xdtd.reshape(bc, G, H // G, Q, P)).reshape(bc * H, N, P)
 
 
+_SSD_STATE_BWD_MODES = ("gemm", "fused")
+_ssd_state_bwd_mode = None
+
+
+def ssd_chunk_state_backward(mode=None):
+    """Get/set the process-wide backward of the chunk-state kernel: "gemm"
+    (default) runs the two einsums autograd runs for the states einsum,
+    "fused" runs the kernel of ops/hip/ssd_state_bwd.hip. None = query.
+    Returns the previous mode; until it is set, FMS_AMD_SSD_STATE_BWD gives
+    the mode."""
+    global _ssd_state_bwd_mode
+    prev = _ssd_state_bwd_mode
+    if prev is None:
+        prev = os.environ.get("FMS_AMD_SSD_STATE_BWD") or "gemm"
+        if prev not in _SSD_STATE_BWD_MODES:
+            raise ValueError(f"FMS_AMD_SSD_STATE_BWD must be one of "
+                             f"{_SSD_STATE_BWD_MODES}, got {prev!r}")
+    if mode is not None:
+        if mode not in _SSD_STATE_BWD_MODES:
+            raise ValueError(f"ssd_chunk_state_backward: mode must be one of "
+                             f"{_SSD_STATE_BWD_MODES}, got {mode!r}")
+        _ssd_state_bwd_mode = mode
+    return prev
+
+
 class _SSDChunkStateFn(torch.autograd.Function):
-    """states (bc*H, N, P) from ssd_chunk_state_kernel. The backward is the
-    pair of einsums autograd runs for the states einsum: dxdtd from B and
-    dS, dB from xdtd and dS summed over the heads of a group."""
+    """states (bc*H, N, P) from ssd_chunk_state_kernel. The backward depends
+    on ssd_chunk_state_backward(). "gemm" is the pair of einsums autograd
+    runs for the states einsum: dxdtd from B and dS, dB from xdtd and dS
+    summed over the heads of a group. "fused" is ops/hip/ssd_state_bwd.hip:
+    both gradients from one staging of a bf16 dS, dB as fp32 partials per
+    head block that are summed here."""
 
     @staticmethod
     def forward(ctx, B2d, xdtd, H, G, P, N, Q):
@@ -1493,6 +1521,12 @@ class _SSDChunkStateFn(torch.autograd.Function):
     def backward(ctx, dS):
         B2d, xdtd = ctx.saved_tensors
         H, G, P, N, Q = ctx.meta
+        if ssd_chunk_state_backward() == "fused":
+            ext = _require_ext("ssd_chunk_state_bwd")
+            dBp, dxdtd = ext.ssd_chunk_state_bwd(
+                dS.contiguous().to(torch.bfloat16), B2d, xdtd, H, G, P, N, Q)
+            return (dBp.sum(0).to(B2d.dtype), dxdtd.view(xdtd.shape),
+                    None, None, None, None, None)
         bc = B2d.shape[0] // Q
         rep = H // G
         dS5 = dS.reshape(bc, G, rep, N, P)

@@ -123,6 +123,9 @@ int ssd_chunk_state_plan(long long, int, int*);
 void launch_ssd_chunk_state(const void*, const void*, void*, long long, int,
                             int, int, int, int, long long, int, int,
                             hipStream_t);
+void launch_ssd_chunk_state_bwd(const void*, const void*, const void*, float*,
+                                void*, long long, int, int, int, int, int,
+                                long long, int, hipStream_t);
 int ssd_state_pass_block(int, int);
 void launch_ssd_state_pass_fwd(const void*, const float*, const float*, void*,
                                float*, const int*, long long, int, int, int,
@@ -1702,6 +1705,62 @@ Tensor ssd_chunk_state(Tensor B, Tensor xdtd, int64_t H, int64_t G, int64_t P,
   return S;
 }
 
+// ---- backward of the chunk states (ssd_state_bwd.hip) --------------------
+static int64_t ssd_chunk_state_bwd_count = 0;
+
+// Launches of ssd_chunk_state_bwd_kernel so far (not part of
+// ssd_state_calls()).
+int64_t ssd_chunk_state_bwd_calls() { return ssd_chunk_state_bwd_count; }
+
+// dS (bc*H, N, P) bf16 contiguous; B and xdtd as ssd_chunk_state. Returns
+// the dB partials (nhb, bc*Q, G*N) fp32, to be summed over dim 0, and dxdtd
+// bf16 in xdtd's shape. head_blocks = 0 takes ssd_diag_bwd's plan.
+std::tuple<Tensor, Tensor> ssd_chunk_state_bwd(
+    Tensor dS, Tensor B, Tensor xdtd, int64_t H, int64_t G, int64_t P,
+    int64_t N, int64_t Q, int64_t head_blocks) {
+  const char* op = "ssd_chunk_state_bwd";
+  TORCH_CHECK(H > 0 && G > 0 && H % G == 0, op,
+              ": H must be a multiple of G");
+  TORCH_CHECK(N > 0 && P > 0 && N <= 256 && P <= 256 &&
+                  ssd_diag_supported((int)N, (int)P),
+              op, ": no kernel for N = ", N, ", P = ", P);
+  TORCH_CHECK(Q >= 32 && Q <= 256 && Q % 32 == 0, op,
+              ": Q must be a multiple of 32 in [32, 256], got ", Q);
+  TORCH_CHECK(head_blocks >= 0 && head_blocks <= H / G, op,
+              ": head_blocks must lie in [0, H/G], got ", head_blocks);
+  TORCH_CHECK(xdtd.is_cuda(), op, ": xdtd must be on a GPU");
+  TORCH_CHECK(B.dim() == 2 && B.size(0) % Q == 0, op,
+              ": B rows must be a multiple of Q");
+  const long long rows = B.size(0);
+  const long long bc = rows / Q;
+  const long long sB = check_diag_slice(B, rows, G * N, xdtd, "B");
+  TORCH_CHECK(sB < (1LL << 24), op, ": row stride of B too large");
+  check_bf16_numel(xdtd, rows * H * P, "xdtd");
+  check_bf16_numel(dS, bc * H * N * P, "dS");
+  TORCH_CHECK(dS.is_cuda() && dS.device() == xdtd.device(), op,
+              ": dS must be on the GPU of xdtd");
+  TORCH_CHECK(aligned16(xdtd) && aligned16(dS), op,
+              ": xdtd and dS must be 16-byte aligned");
+  const long long base = bc * G * ((Q + 127) / 128);
+  TORCH_CHECK(base * (H / G) < (1LL << 31), op,
+              ": too many chunks for one grid");
+  int nhb = (int)head_blocks;
+  if (nhb == 0)
+    nhb = ssd_diag_bwd_plan(base, (int)(H / G),
+                            ssd_diag_bwd_cus(xdtd.get_device()),
+                            SSD_DIAG_BWD_WGS_PER_CU);
+  auto dBp = torch::empty({nhb, rows, G * N},
+                          xdtd.options().dtype(torch::kFloat32));
+  auto dxdtd = torch::empty_like(xdtd);
+  if (bc == 0) return {dBp, dxdtd};
+  launch_ssd_chunk_state_bwd(dS.data_ptr(), B.data_ptr(), xdtd.data_ptr(),
+                             dBp.data_ptr<float>(), dxdtd.data_ptr(), bc,
+                             (int)H, (int)G, (int)P, (int)N, (int)Q, sB, nhb,
+                             cur_stream());
+  ++ssd_chunk_state_bwd_count;
+  return {dBp, dxdtd};
+}
+
 // whether the state-pass kernels serve (N, P): 8 consecutive (k, p) elements
 // per thread inside one state row, whole 64-thread waves per (b, h)
 bool ssd_state_pass_has_kernel(int64_t N, int64_t P) {
@@ -1864,6 +1923,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("out") = py::none());
   mod.def("ssd_chunk_state_has_kernel", &ssd_chunk_state_has_kernel);
   mod.def("ssd_state_calls", &ssd_state_calls);
+  mod.def("ssd_chunk_state_bwd", &ssd_chunk_state_bwd, py::arg("dS"),
+          py::arg("B"), py::arg("xdtd"), py::arg("H"), py::arg("G"),
+          py::arg("P"), py::arg("N"), py::arg("Q"),
+          py::arg("head_blocks") = 0);
+  mod.def("ssd_chunk_state_bwd_calls", &ssd_chunk_state_bwd_calls);
   mod.def("ssd_state_pass_has_kernel", &ssd_state_pass_has_kernel);
   mod.def("ssd_state_pass_fwd", &ssd_state_pass_fwd);
   mod.def("ssd_state_pass_fwd_doc", &ssd_state_pass_fwd_doc);

@@ -42,6 +42,7 @@ def main(**kwargs):
     ops.attn_bwd_workspace_limit(cfg.attn_bwd_workspace_mb)
     ops.ssd_diag_backward(cfg.ssd_diag_bwd)
     ops.ssd_state_chain(cfg.ssd_state_chain)
+    ops.ssd_chunk_state_backward(cfg.ssd_chunk_state_bwd)
 
     if rank == 0:
         print(f"--> running with these configs {cfg}")

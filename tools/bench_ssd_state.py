@@ -10,13 +10,18 @@ buffer, as the model passes it.
 (2) `cont`: a 4096-token continuation of a Mamba2Mixer over a cache in use,
 every token through ops.ssd_state_update (FMS_AMD_MAMBA_PREFILL=step)
 against the chunked scan from the cached state.
+(3) `cs_bwd`: the backward of ops.ssd_chunk_state alone (its graph is built
+outside the timed region), under ops.ssd_chunk_state_backward("gemm") (the
+two einsums) and ("fused") (ops/hip/ssd_state_bwd.hip with the sum of its
+head-block partials and the cast).
 
 The routes alternate inside ONE process: --repeats rounds, each timing
 --iters calls per route with device events; medians and max-min spreads are
 reported. Every call takes the next of --sets operand sets, so the inputs
 of a call have left the 256 MB last-level cache since their last use.
 
-Run on GPU: python tools/bench_ssd_state.py [--json OUT]"""
+Run on GPU: python tools/bench_ssd_state.py [--cases chain cs_bwd cont]
+[--json OUT]"""
 
 import argparse
 import json
@@ -64,7 +69,7 @@ def chain_fused(Bm, xdtd, dacs, H):
     return ops.ssd_state_pass(states, dacs, B, H, P, N_STATE, Q)
 
 
-def chain_cases(H, nsets):
+def operand_sets(H, nsets):
     def operand_set():
         conv = torch.randn(B * L, H * P + 2 * G * N_STATE, device="cuda",
                            dtype=torch.bfloat16)
@@ -74,7 +79,11 @@ def chain_cases(H, nsets):
                 -(torch.rand(nrow, Q, device="cuda") * 0.05).cumsum(-1),
                 torch.randn(B, NC, H, N_STATE, P, device="cuda",
                             dtype=torch.bfloat16))
-    sets = [operand_set() for _ in range(nsets)]
+    return [operand_set() for _ in range(nsets)]
+
+
+def chain_cases(H, nsets):
+    sets = operand_sets(H, nsets)
     turn = [0]
 
     def call(fn, grad):
@@ -91,6 +100,24 @@ def chain_cases(H, nsets):
     return {pat: {r: (lambda fn=fn, grad=grad: call(fn, grad))
                   for r, fn in (("gemm", chain_gemm), ("fused", chain_fused))}
             for pat, grad in (("fwd", False), ("fwd+bwd", True))}
+
+
+def cs_bwd_cases(H, nsets):
+    sets = []
+    for Bm, xdtd, _, dS in operand_sets(H, nsets):
+        leaves = [Bm.detach().requires_grad_(), xdtd.requires_grad_()]
+        S = ops.ssd_chunk_state(*leaves, H, G, P, N_STATE, Q)
+        sets.append((S, leaves, dS.view_as(S)))
+    turn = [0]
+
+    def call(mode):
+        S, leaves, dS = sets[turn[0] % nsets]
+        turn[0] += 1
+        prev = ops.ssd_chunk_state_backward(mode)
+        torch.autograd.grad(S, leaves, dS, retain_graph=True)
+        ops.ssd_chunk_state_backward(prev)
+
+    return {"cs_bwd": {r: (lambda r=r: call(r)) for r in ("gemm", "fused")}}
 
 
 def cont_cases(H, nsets):
@@ -118,6 +145,9 @@ def cont_cases(H, nsets):
     return {"cont": {r: (lambda r=r: call(r)) for r in ("step", "chunked")}}
 
 
+CASES = {"chain": chain_cases, "cs_bwd": cs_bwd_cases, "cont": cont_cases}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -125,6 +155,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--sets", type=int, default=3)
     ap.add_argument("--heads", type=int, nargs="+", default=[80, 128])
+    ap.add_argument("--cases", nargs="+", default=list(CASES),
+                    choices=list(CASES))
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     prefill = os.environ.get("FMS_AMD_MAMBA_PREFILL")
@@ -132,7 +164,7 @@ def main():
     print(f"b{B} l{L} P{P} G{G} n{N_STATE} Q{Q}; ms per call, median of "
           f"{args.repeats} rounds x {args.iters} calls (spread = max - min)")
     for H in args.heads:
-        for cases in (chain_cases, cont_cases):
+        for cases in (CASES[c] for c in args.cases):
             for pat, routes in cases(H, args.sets).items():
                 samples = {r: [] for r in routes}
                 for _ in range(args.repeats):
