@@ -131,3 +131,7 @@ class train_config:
     # of ops/hip/ssd_state_bwd.hip. Applied once at start-up through
     # ops.ssd_chunk_state_backward().
     ssd_chunk_state_bwd: str = "gemm"
+    # The y_off product of the scan, forward and backward: "gemm" is the
+    # einsum on hipBLASLt, "fused" runs the kernels of ops/hip/ssd_yoff.hip.
+    # Applied once at start-up through ops.ssd_yoff_mode().
+    ssd_yoff: str = "gemm"

@@ -272,9 +272,10 @@ class Mamba2Mixer(nn.Module):
         """GPU SSD scan: the elementwise chains run as fused HIP kernels
         (ops/hip/ssd.hip — prep/xdt/ygate, each with a custom backward),
         the intra-chunk term y_diag as the fused MFMA kernel of
-        ops/hip/ssd_diag.hip; only the other MFMA-shaped work (states,
+        ops/hip/ssd_diag.hip; by default the other MFMA-shaped work (states,
         y_off einsums on hipBLASLt) and the tiny nc x nc
-        inter-chunk recurrence stay as torch ops. Inputs x/dt/z/B/C are
+        inter-chunk recurrence stay as torch ops (ops.ssd_state_chain and
+        ops.ssd_yoff_mode move them to kernels). Inputs x/dt/z/B/C are
         STRIDED slices of the fused projections — no contiguous copies.
         Returns the gated (b, l, d_inner) bf16 activations (pre-norm).
         doc_start/doc_end (a DocMask's arrays) reset the scan at every
@@ -293,7 +294,6 @@ class Mamba2Mixer(nn.Module):
         g, n = self.ngroups, self.d_state
         Q = self.chunk
         nc = l // Q
-        rep = h // g
         dt2 = dt.reshape(b * l, h)
         x2 = x.reshape(b * l, h * p)
         z2 = z.reshape(b * l, h * p)
@@ -303,7 +303,6 @@ class Mamba2Mixer(nn.Module):
         xdt, xdtd = ops.ssd_xdt(x2, dtf, dacs, h, p, Q,    # bf16 pair
                                 doc_mask=doc_mask)
         Bm = B.reshape(b, nc, Q, g, n)
-        Cm = C.reshape(b, nc, Q, g, n)
         # intra-chunk term: scores per GROUP (g << h), decay and the
         # product with xdt in one kernel (ops/hip/ssd_diag.hip; neither
         # the scores nor sL reach HBM). B/C are read in place.
@@ -317,10 +316,10 @@ class Mamba2Mixer(nn.Module):
             prev, final = self._state_chain_gemm(
                 b, nc, Bm, xdtd, dacs, doc_start, return_final_state)
         # output ordering "bcgqrp" = the bmm-natural layout; the ygate
-        # kernel reads it in place
-        y_off = torch.einsum(
-            "bcqgn,bcgrnp->bcgqrp", Cm,
-            prev.view(b, nc, g, rep, n, p))
+        # kernel reads it in place (einsum on hipBLASLt, or the kernels of
+        # ops/hip/ssd_yoff.hip under ops.ssd_yoff_mode("fused"))
+        y_off = ops.ssd_yoff(C.reshape(b * l, g * n), prev, h, g, p, n, Q,
+                             b=b)
         out = ops.ssd_ygate(
             y_diag.reshape(b * l, h * p),
             y_off.contiguous().view(b * l, h * p),

@@ -1553,6 +1553,80 @@ def ssd_chunk_state(B2d, xdtd, H, G, P, N, Q):
     return _ssd_chunk_state_gemm(B2d, xdtd, H, G, P, N, Q)
 
 
+_SSD_YOFF_MODES = ("gemm", "fused")
+_ssd_yoff_mode = None
+
+
+def ssd_yoff_mode(mode=None):
+    """Get/set the process-wide route of the y_off product of the fused scan
+    (ssd_yoff): "gemm" (default) is the einsum on hipBLASLt, "fused" runs
+    the kernels of ops/hip/ssd_yoff.hip, forward and backward. None = query.
+    Returns the previous mode; until it is set, FMS_AMD_SSD_YOFF gives the
+    mode."""
+    global _ssd_yoff_mode
+    prev = _ssd_yoff_mode
+    if prev is None:
+        prev = os.environ.get("FMS_AMD_SSD_YOFF") or "gemm"
+        if prev not in _SSD_YOFF_MODES:
+            raise ValueError(f"FMS_AMD_SSD_YOFF must be one of "
+                             f"{_SSD_YOFF_MODES}, got {prev!r}")
+    if mode is not None:
+        if mode not in _SSD_YOFF_MODES:
+            raise ValueError(f"ssd_yoff_mode: mode must be one of "
+                             f"{_SSD_YOFF_MODES}, got {mode!r}")
+        _ssd_yoff_mode = mode
+    return prev
+
+
+class _SSDYOffFn(torch.autograd.Function):
+    """yoff (bc, G, Q, rep, P) from ssd_yoff_fwd_kernel; the backward is
+    ssd_yoff_dprev_kernel and ssd_yoff_dC_kernel on a bf16 dyoff, dC as
+    fp32 partials per head block that are summed here."""
+
+    @staticmethod
+    def forward(ctx, C2d, prev, H, G, P, N, Q):
+        ext = _require_ext("ssd_yoff")
+        yoff = ext.ssd_yoff_fwd(C2d, prev, H, G, P, N, Q)
+        ctx.save_for_backward(C2d, prev)
+        ctx.meta = (H, G, P, N, Q)
+        return yoff
+
+    @staticmethod
+    def backward(ctx, dyoff):
+        C2d, prev = ctx.saved_tensors
+        need_dC, need_dprev = ctx.needs_input_grad[:2]
+        ext = _require_ext("ssd_yoff")
+        dCp, dprev = ext.ssd_yoff_bwd(
+            dyoff.contiguous().to(torch.bfloat16), C2d, prev, *ctx.meta,
+            need_dC=need_dC, need_dprev=need_dprev)
+        return (dCp.sum(0).to(C2d.dtype) if need_dC else None,
+                dprev.view(prev.shape) if need_dprev else None,
+                None, None, None, None, None)
+
+
+def ssd_yoff(C2d, prev, H, G, P, N, Q, b=1):
+    """The y_off product of the SSD before its decay, (bc, G, Q, rep, P) on
+    every route: yoff[bc, g, q, r] = C[bc*Q + q, g] . prev[bc*H + g*rep + r]
+    (reference.ssd_yoff has the definition), the element order ssd_ygate
+    reads as (b*l, H*P). C2d (b*l, G*N) may be a last-dim slice of the conv
+    output; prev holds (b*l/Q*H, N, P) states in any shape with that element
+    order. Under ssd_yoff_mode() "fused", bf16 GPU tensors of the shapes
+    ssd_diag serves run the kernels of ops/hip/ssd_yoff.hip. Every other
+    case is the einsum of the scan on views split into `b` sequences (so
+    that it issues the same bmm whatever the caller's batch), with its two
+    leading dimensions merged; like the einsum's own output the result is
+    not necessarily contiguous."""
+    if ssd_yoff_mode() == "fused" and prev.is_cuda \
+            and prev.dtype == torch.bfloat16 \
+            and C2d.dtype == torch.bfloat16 \
+            and _require_ext("ssd_yoff").ssd_yoff_has_kernel(N, P, Q):
+        return _SSDYOffFn.apply(_ssd_diag_view(C2d), prev.contiguous(),
+                                H, G, P, N, Q)
+    nc = C2d.shape[0] // (b * Q)
+    return torch.einsum("bcqgn,bcgrnp->bcgqrp", C2d.reshape(b, nc, Q, G, N),
+                        prev.view(b, nc, G, H // G, N, P)).flatten(0, 1)
+
+
 class _SSDStatePassFn(torch.autograd.Function):
     """prev (b*nc*H, N, P) bf16 and the fp32 final state from
     ssd_state_pass_fwd_kernel; the backward is the reverse scan of

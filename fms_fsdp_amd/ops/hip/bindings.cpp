@@ -126,6 +126,15 @@ void launch_ssd_chunk_state(const void*, const void*, void*, long long, int,
 void launch_ssd_chunk_state_bwd(const void*, const void*, const void*, float*,
                                 void*, long long, int, int, int, int, int,
                                 long long, int, hipStream_t);
+int ssd_yoff_plan(long long, int, int, int, int*);
+int ssd_yoff_dprev_cap(int, int);
+void launch_ssd_yoff_fwd(const void*, const void*, void*, long long, int, int,
+                         int, int, int, long long, int, int, hipStream_t);
+void launch_ssd_yoff_dprev(const void*, const void*, void*, long long, int,
+                           int, int, int, int, long long, int, int,
+                           hipStream_t);
+void launch_ssd_yoff_dC(const void*, const void*, float*, long long, int, int,
+                        int, int, int, int, hipStream_t);
 int ssd_state_pass_block(int, int);
 void launch_ssd_state_pass_fwd(const void*, const float*, const float*, void*,
                                float*, const int*, long long, int, int, int,
@@ -1761,6 +1770,119 @@ std::tuple<Tensor, Tensor> ssd_chunk_state_bwd(
   return {dBp, dxdtd};
 }
 
+// ---- y_off term (ssd_yoff.hip) -------------------------------------------
+static int64_t ssd_yoff_count = 0;
+
+// Calls of ssd_yoff_fwd / ssd_yoff_bwd that launched, one each.
+int64_t ssd_yoff_calls() { return ssd_yoff_count; }
+
+// whether ops.ssd_yoff may send (N, P, Q) to the kernels
+bool ssd_yoff_has_kernel(int64_t N, int64_t P, int64_t Q) {
+  return ssd_diag_has_kernel(N, P, Q);
+}
+
+// shared argument checks; returns bc and stores C's row stride
+static long long check_yoff(const char* op, const Tensor& C,
+                            const Tensor& prev, int64_t H, int64_t G,
+                            int64_t P, int64_t N, int64_t Q, long long* sC) {
+  TORCH_CHECK(H > 0 && G > 0 && H % G == 0, op,
+              ": H must be a multiple of G");
+  TORCH_CHECK(N > 0 && P > 0 && N <= 256 && P <= 256 &&
+                  ssd_diag_supported((int)N, (int)P),
+              op, ": no kernel for N = ", N, ", P = ", P);
+  TORCH_CHECK(Q >= 32 && Q <= 256 && Q % 32 == 0, op,
+              ": Q must be a multiple of 32 in [32, 256], got ", Q);
+  TORCH_CHECK(prev.is_cuda(), op, ": prev must be on a GPU");
+  // C's view rule is check_diag_slice's, spelled out in this op's words
+  TORCH_CHECK(C.scalar_type() == torch::kBFloat16 && C.dim() == 2 &&
+                  C.stride(1) == 1,
+              op, ": C must be bf16, 2-D and row-major");
+  TORCH_CHECK(C.is_cuda() && C.device() == prev.device(), op,
+              ": C must be on the GPU of prev");
+  TORCH_CHECK(C.size(0) % Q == 0 && C.size(1) == G * N, op,
+              ": C must have shape (bc*Q, G*N), got (", C.size(0), ", ",
+              C.size(1), ")");
+  const long long bc = C.size(0) / Q;
+  *sC = C.stride(0);
+  TORCH_CHECK(*sC >= G * N && *sC % 8 == 0 && aligned16(C), op,
+              ": C needs a row stride that is a multiple of 8 elements and "
+              "a 16-byte aligned base");
+  TORCH_CHECK(*sC < (1LL << 24), op, ": row stride of C too large");
+  check_bf16_numel(prev, bc * H * N * P, "prev");
+  TORCH_CHECK(aligned16(prev), op, ": prev must be 16-byte aligned");
+  TORCH_CHECK(bc * G * ((Q + 127) / 128) * (H / G) < (1LL << 31), op,
+              ": too many chunks for one grid");
+  return bc;
+}
+
+// yoff (bc, G, Q, rep, P) bf16 = C prev per (chunk, head), the layout
+// ssd_ygate reads as (bc*Q, H*P). C (b*l, G*N) bf16 last-dim slice read in
+// place (the rule of check_diag_slice); prev (bc*H, N, P) bf16 contiguous in
+// any shape with that element order.
+Tensor ssd_yoff_fwd(Tensor C, Tensor prev, int64_t H, int64_t G, int64_t P,
+                    int64_t N, int64_t Q) {
+  const char* op = "ssd_yoff_fwd";
+  long long sC = 0;
+  const long long bc = check_yoff(op, C, prev, H, G, P, N, Q, &sC);
+  auto yoff = torch::empty({bc, G, Q, H / G, P}, prev.options());
+  if (bc == 0) return yoff;
+  int HB = 1;
+  const int nhb = ssd_yoff_plan(
+      bc * G * ((Q + 127) / 128), (int)(H / G), 8,
+      SSD_DIAG_BWD_WGS_PER_CU * ssd_diag_bwd_cus(prev.get_device()), &HB);
+  launch_ssd_yoff_fwd(C.data_ptr(), prev.data_ptr(), yoff.data_ptr(), bc,
+                      (int)H, (int)G, (int)P, (int)N, (int)Q, sC, HB, nhb,
+                      cur_stream());
+  ++ssd_yoff_count;
+  return yoff;
+}
+
+// dyoff bf16 contiguous in yoff's element order. Returns the dC partials
+// (nhb, bc*Q, G*N) fp32, to be summed over dim 0, and dprev bf16 in prev's
+// shape. head_blocks = 0 takes ssd_diag_bwd's plan. need_dC / need_dprev =
+// false skips that kernel and returns an empty tensor in its place.
+std::tuple<Tensor, Tensor> ssd_yoff_bwd(Tensor dyoff, Tensor C, Tensor prev,
+                                        int64_t H, int64_t G, int64_t P,
+                                        int64_t N, int64_t Q,
+                                        int64_t head_blocks, bool need_dC,
+                                        bool need_dprev) {
+  const char* op = "ssd_yoff_bwd";
+  long long sC = 0;
+  const long long bc = check_yoff(op, C, prev, H, G, P, N, Q, &sC);
+  TORCH_CHECK(head_blocks >= 0 && head_blocks <= H / G, op,
+              ": head_blocks must lie in [0, H/G], got ", head_blocks);
+  check_bf16_numel(dyoff, bc * Q * H * P, "dyoff");
+  TORCH_CHECK(dyoff.is_cuda() && dyoff.device() == prev.device() &&
+                  aligned16(dyoff),
+              op, ": dyoff must be 16-byte aligned on the GPU of prev");
+  const long long base = bc * G * ((Q + 127) / 128);
+  const int cus = ssd_diag_bwd_cus(prev.get_device());
+  int nhb = (int)head_blocks;
+  if (nhb == 0)
+    nhb = ssd_diag_bwd_plan(base, (int)(H / G), cus, SSD_DIAG_BWD_WGS_PER_CU);
+  auto dCp = need_dC ? torch::empty({nhb, bc * Q, G * N},
+                                    prev.options().dtype(torch::kFloat32))
+                     : torch::empty({0}, prev.options().dtype(torch::kFloat32));
+  auto dprev = need_dprev ? torch::empty_like(prev)
+                          : torch::empty({0}, prev.options());
+  if (bc == 0 || !(need_dC || need_dprev)) return {dCp, dprev};
+  if (need_dprev) {
+    int HB = 1;
+    const int nhd = ssd_yoff_plan(bc * G, (int)(H / G),
+                                  ssd_yoff_dprev_cap((int)N, (int)P),
+                                  SSD_DIAG_BWD_WGS_PER_CU * cus, &HB);
+    launch_ssd_yoff_dprev(dyoff.data_ptr(), C.data_ptr(), dprev.data_ptr(),
+                          bc, (int)H, (int)G, (int)P, (int)N, (int)Q, sC, HB,
+                          nhd, cur_stream());
+  }
+  if (need_dC)
+    launch_ssd_yoff_dC(dyoff.data_ptr(), prev.data_ptr(),
+                       dCp.data_ptr<float>(), bc, (int)H, (int)G, (int)P,
+                       (int)N, (int)Q, nhb, cur_stream());
+  ++ssd_yoff_count;
+  return {dCp, dprev};
+}
+
 // whether the state-pass kernels serve (N, P): 8 consecutive (k, p) elements
 // per thread inside one state row, whole 64-thread waves per (b, h)
 bool ssd_state_pass_has_kernel(int64_t N, int64_t P) {
@@ -1928,6 +2050,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("P"), py::arg("N"), py::arg("Q"),
           py::arg("head_blocks") = 0);
   mod.def("ssd_chunk_state_bwd_calls", &ssd_chunk_state_bwd_calls);
+  mod.def("ssd_yoff_has_kernel", &ssd_yoff_has_kernel);
+  mod.def("ssd_yoff_fwd", &ssd_yoff_fwd, py::arg("C"), py::arg("prev"),
+          py::arg("H"), py::arg("G"), py::arg("P"), py::arg("N"),
+          py::arg("Q"));
+  mod.def("ssd_yoff_bwd", &ssd_yoff_bwd, py::arg("dyoff"), py::arg("C"),
+          py::arg("prev"), py::arg("H"), py::arg("G"), py::arg("P"),
+          py::arg("N"), py::arg("Q"), py::arg("head_blocks") = 0,
+          py::arg("need_dC") = true, py::arg("need_dprev") = true);
+  mod.def("ssd_yoff_calls", &ssd_yoff_calls);
   mod.def("ssd_state_pass_has_kernel", &ssd_state_pass_has_kernel);
   mod.def("ssd_state_pass_fwd", &ssd_state_pass_fwd);
   mod.def("ssd_state_pass_fwd_doc", &ssd_state_pass_fwd_doc);

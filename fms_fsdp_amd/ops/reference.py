@@ -254,6 +254,17 @@ def ssd_chunk_state(B2d, xdtd, H, G, P, N, Q):
     return S.reshape(bc * H, N, P)
 
 
+def ssd_yoff(C2d, prev, H, G, P, N, Q):
+    """The y_off product (bc, G, Q, rep, P) in the input dtype (oracle of
+    the ssd_yoff kernels): yoff[bc, g, q, r, p] = sum_k C[bc*Q + q, g*N + k]
+    prev[m, k, p], m = bc*H + g*rep + r, rep = H // G. prev (bc*H, N, P) in
+    any shape with that element order. Decay and document mask are applied
+    by ssd_ygate."""
+    bc = C2d.shape[0] // Q
+    return torch.einsum("cqgn,cgrnp->cgqrp", C2d.reshape(bc, Q, G, N),
+                        prev.reshape(bc, G, H // G, N, P))
+
+
 def ssd_state_pass(states, dacs, b, H, P, N, Q, doc_mask=None,
                    initial_state=None, return_final_state=False):
     """The inter-chunk recurrence (oracle of the ssd_state_pass kernels).

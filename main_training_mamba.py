@@ -43,6 +43,7 @@ def main(**kwargs):
     ops.ssd_diag_backward(cfg.ssd_diag_bwd)
     ops.ssd_state_chain(cfg.ssd_state_chain)
     ops.ssd_chunk_state_backward(cfg.ssd_chunk_state_bwd)
+    ops.ssd_yoff_mode(cfg.ssd_yoff)
 
     if rank == 0:
         print(f"--> running with these configs {cfg}")

@@ -14,13 +14,18 @@ against the chunked scan from the cached state.
 outside the timed region), under ops.ssd_chunk_state_backward("gemm") (the
 two einsums) and ("fused") (ops/hip/ssd_state_bwd.hip with the sum of its
 head-block partials and the cast).
+(4) `yoff`: ops.ssd_yoff under ops.ssd_yoff_mode("gemm") (the einsum of
+Mamba2Mixer._scan_fused on hipBLASLt) and ("fused") (ops/hip/ssd_yoff.hip);
+`fwd` is the no-grad forward, `fwd+bwd` the forward with a graph and its
+backward (for "fused" with the sum of the dC partials and the cast). C is a
+last-dim slice of a conv-output sized buffer.
 
 The routes alternate inside ONE process: --repeats rounds, each timing
 --iters calls per route with device events; medians and max-min spreads are
 reported. Every call takes the next of --sets operand sets, so the inputs
 of a call have left the 256 MB last-level cache since their last use.
 
-Run on GPU: python tools/bench_ssd_state.py [--cases chain cs_bwd cont]
+Run on GPU: python tools/bench_ssd_state.py [--cases chain cs_bwd cont yoff]
 [--json OUT]"""
 
 import argparse
@@ -145,7 +150,36 @@ def cont_cases(H, nsets):
     return {"cont": {r: (lambda r=r: call(r)) for r in ("step", "chunked")}}
 
 
-CASES = {"chain": chain_cases, "cs_bwd": cs_bwd_cases, "cont": cont_cases}
+def yoff_cases(H, nsets):
+    sets = []
+    for Cm, dy, _, prev in operand_sets(H, nsets):
+        # dyoff has the element count of an h-major activation
+        sets.append((Cm, prev.view(B * NC * H, N_STATE, P), dy))
+    turn = [0]
+
+    def call(mode, grad):
+        Cm, prev, dy = sets[turn[0] % nsets]
+        turn[0] += 1
+        old = ops.ssd_yoff_mode(mode)
+        try:
+            if grad:
+                leaves = [Cm.detach().requires_grad_(),
+                          prev.detach().requires_grad_()]
+                y = ops.ssd_yoff(*leaves, H, G, P, N_STATE, Q, b=B)
+                torch.autograd.grad(y, leaves, dy.view_as(y))
+            else:
+                with torch.no_grad():
+                    ops.ssd_yoff(Cm, prev, H, G, P, N_STATE, Q, b=B)
+        finally:
+            ops.ssd_yoff_mode(old)
+
+    return {"yoff " + pat: {r: (lambda r=r, grad=grad: call(r, grad))
+                            for r in ("gemm", "fused")}
+            for pat, grad in (("fwd", False), ("fwd+bwd", True))}
+
+
+CASES = {"chain": chain_cases, "cs_bwd": cs_bwd_cases, "cont": cont_cases,
+         "yoff": yoff_cases}
 
 
 def main():
@@ -171,7 +205,7 @@ def main():
                     for r, fn in routes.items():
                         samples[r].append(event_ms(fn, args.iters,
                                                    args.warmup))
-                line = f"  H{H:<4d}{pat:8s}"
+                line = f"  H{H:<4d}{pat:13s}"
                 base = statistics.median(next(iter(samples.values())))
                 for r, x in samples.items():
                     med, spread = statistics.median(x), max(x) - min(x)
