@@ -60,6 +60,11 @@ class MoEMLP(nn.Module):
     def forward(self, x):
         b, s, e = x.shape
         flat = x.view(-1, e)
+        fused = ops.moe_mlp(flat, self.router.weight,
+                            [lin.weight for lin in self.wg1],
+                            [lin.weight for lin in self.w2], self.top_k)
+        if fused is not None:       # ops.moe_mode("fused"), inference
+            return fused.view(b, s, e)
         logits = self.router(flat).float()
         weights, experts = torch.topk(torch.softmax(logits, -1), self.top_k, -1)
         weights = weights / weights.sum(-1, keepdim=True)

@@ -1627,6 +1627,67 @@ def ssd_yoff(C2d, prev, H, G, P, N, Q, b=1):
                         prev.view(b, nc, G, H // G, N, P)).flatten(0, 1)
 
 
+_MOE_MODES = ("loop", "fused")
+_moe_mode = None
+
+
+def moe_mode(mode=None):
+    """Get/set the process-wide route of the Mixtral MoE MLP: "loop"
+    (default) is the per-expert loop of MoEMLP.forward, "fused" runs the
+    inference kernels of ops/hip/moe.hip where moe_mlp applies. None = query.
+    Returns the previous mode; until it is set, FMS_AMD_MOE gives the mode."""
+    global _moe_mode
+    prev = _moe_mode
+    if prev is None:
+        prev = os.environ.get("FMS_AMD_MOE") or "loop"
+        if prev not in _MOE_MODES:
+            raise ValueError(f"FMS_AMD_MOE must be one of {_MOE_MODES}, "
+                             f"got {prev!r}")
+    if mode is not None:
+        if mode not in _MOE_MODES:
+            raise ValueError(f"moe_mode: mode must be one of {_MOE_MODES}, "
+                             f"got {mode!r}")
+        _moe_mode = mode
+    return prev
+
+
+def moe_mlp(x2d, router_weight, wg1_list, w2_list, top_k):
+    """The routed SwiGLU MoE forward of x2d (T, emb) on the kernels of
+    ops/hip/moe.hip (reference.moe_mlp has the definition; the routing is
+    the top_k of the fp32 softmax of the router logits, renormalised), or
+    None where that path does not apply and the caller runs its loop. It
+    applies under moe_mode() "fused" to contiguous bf16 GPU tensors with
+    emb and H multiples of 64, at most 16 experts of one shape and
+    top_k <= min(4, experts), when nothing needs a gradient: there is no
+    backward. wg1_list[e] (2H, emb) and w2_list[e] (emb, H) are read in
+    place."""
+    if moe_mode() != "fused":
+        return None
+    ws = [router_weight, *wg1_list, *w2_list]
+    if not x2d.is_cuda or any(t.dtype != torch.bfloat16 or
+                              t.device != x2d.device for t in [x2d, *ws]):
+        return None
+    if torch.is_grad_enabled() and any(t.requires_grad for t in [x2d, *ws]):
+        return None
+    nE = len(wg1_list)
+    if x2d.dim() != 2 or not 1 <= nE <= 16 or len(w2_list) != nE \
+            or not 1 <= top_k <= min(4, nE):
+        return None
+    T, emb = x2d.shape
+    H = w2_list[0].shape[-1]
+    # the kernels address in 64 bits; rows and grid sizes are 32-bit counts
+    if emb % 64 or H % 64 or T * top_k >= 2 ** 30 \
+            or T * top_k * max(emb, H) >= 2 ** 43 \
+            or any(w.shape != (2 * H, emb) for w in wg1_list) \
+            or any(w.shape != (emb, H) for w in w2_list) \
+            or any(not t.is_contiguous() or t.data_ptr() % 16
+                   for t in [x2d, *wg1_list, *w2_list]):
+        return None
+    logits = torch.nn.functional.linear(x2d, router_weight).float()
+    return _require_ext("moe_mlp").moe_mlp(x2d, logits, list(wg1_list),
+                                           list(w2_list), top_k)
+
+
 class _SSDStatePassFn(torch.autograd.Function):
     """prev (b*nc*H, N, P) bf16 and the fp32 final state from
     ssd_state_pass_fwd_kernel; the backward is the reverse scan of

@@ -10,6 +10,7 @@
 
 #include "attn_decode_plan.h"
 #include "attn_ws.h"
+#include "moe_plan.h"
 
 using torch::Tensor;
 
@@ -143,6 +144,18 @@ void launch_ssd_state_pass_bwd(const void*, const float*, const void*,
                                const float*, void*, float*, float*, const int*,
                                long long, int, int, int, int, int,
                                hipStream_t);
+void launch_moe_route(const float*, int*, float*, long long, int, int,
+                      hipStream_t);
+void launch_moe_sort(const int*, int*, int*, int*, long long, int, int, int,
+                     hipStream_t);
+void launch_moe_gate_up(const void* const*, const void*, const int*,
+                        const int*, void*, int, int, int, int, int, int, int,
+                        hipStream_t);
+void launch_moe_down(const void* const*, const void*, const int*, const int*,
+                     const float*, float*, int, int, int, int, int, int,
+                     hipStream_t);
+void launch_moe_combine(const float*, void*, long long, int, int,
+                        hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -2039,7 +2052,260 @@ std::vector<Tensor> ssd_state_pass_bwd_doc(
                                  want_dinitial, doc_start, l);
 }
 
+// ---- routed MoE MLP, inference forward (moe.hip) ---------------------------
+static int64_t moe_count = 0;
+
+// Calls of moe_mlp that ran the chain.
+int64_t moe_calls() { return moe_count; }
+
+static void check_moe_bm(const char* op, int64_t BM) {
+  TORCH_CHECK(BM == MOE_BM_DECODE || BM == MOE_BM_PREFILL, op,
+              ": BM must be ", MOE_BM_DECODE, " or ", MOE_BM_PREFILL, ", got ",
+              BM);
+}
+
+static void check_moe_topk(const char* op, int64_t top_k, int64_t nE) {
+  TORCH_CHECK(nE >= 1 && nE <= MOE_MAX_EXPERTS, op, ": 1 to ",
+              MOE_MAX_EXPERTS, " experts, got ", nE);
+  TORCH_CHECK(top_k >= 1 && top_k <= MOE_MAX_TOPK && top_k <= nE, op,
+              ": top_k must lie in [1, min(", MOE_MAX_TOPK, ", nE)], got ",
+              top_k);
+}
+
+// the experts' weights: bf16, contiguous, (rows, cols) each, 16-byte aligned
+// on the GPU of `ref`; rows = 0 takes the first expert's row count. Stores
+// the base pointers and returns that row count.
+static int64_t check_moe_experts(const char* op, const char* nm,
+                                 const std::vector<Tensor>& ws, int64_t rows,
+                                 int64_t cols, const Tensor& ref,
+                                 const void** ptrs) {
+  TORCH_CHECK(!ws.empty() && ws.size() <= MOE_MAX_EXPERTS, op, ": ", nm,
+              " must hold 1 to ", MOE_MAX_EXPERTS, " experts");
+  if (rows == 0) rows = ws[0].dim() == 2 ? ws[0].size(0) : -1;
+  for (size_t e = 0; e < ws.size(); ++e) {
+    const Tensor& w = ws[e];
+    TORCH_CHECK(w.scalar_type() == torch::kBFloat16 && w.is_contiguous(), op,
+                ": ", nm, "[", e, "] must be contiguous bf16");
+    TORCH_CHECK(w.dim() == 2 && w.size(0) == rows && w.size(1) == cols, op,
+                ": ", nm, "[", e, "] must have shape (", rows, ", ", cols, ")");
+    TORCH_CHECK(w.is_cuda() && w.device() == ref.device() && aligned16(w), op,
+                ": ", nm, "[", e, "] must be 16-byte aligned on the GPU of x");
+    ptrs[e] = w.data_ptr();
+  }
+  return rows;
+}
+
+// the sort's outputs; returns the tile count
+static int64_t check_moe_sorted(const char* op, const Tensor& row_pair,
+                                const Tensor& tile_expert, int64_t BM,
+                                int64_t npairs, int64_t nE,
+                                const Tensor& ref) {
+  for (const Tensor* t : {&row_pair, &tile_expert})
+    TORCH_CHECK(t->scalar_type() == torch::kInt32 && t->is_contiguous() &&
+                    t->dim() == 1 && t->is_cuda() &&
+                    t->device() == ref.device(),
+                op, ": row_pair and tile_expert must be contiguous int32 "
+                    "vectors on the GPU of the rows");
+  const int64_t ntiles = tile_expert.numel();
+  TORCH_CHECK(ntiles == moe_plan_tiles(npairs, BM, nE) &&
+                  row_pair.numel() == ntiles * BM,
+              op, ": row_pair / tile_expert are not moe_sort's for this BM");
+  return ntiles;
+}
+
+static void check_moe_dims(const char* op, int64_t emb, int64_t H,
+                           int64_t npairs, int64_t ntiles, int64_t BM) {
+  TORCH_CHECK(emb > 0 && H > 0 && emb % 64 == 0 && H % 64 == 0, op,
+              ": emb and H must be multiples of 64, got ", emb, " and ", H);
+  // element offsets are 64-bit in the kernels; the counts are ints
+  const int64_t wide = emb > H ? emb : H;
+  TORCH_CHECK(npairs < (1LL << 31) && ntiles * BM < (1LL << 31) &&
+                  ntiles * ((wide + 63) / 64) < (1LL << 31),
+              op, ": too many rows for one grid");
+}
+
+// (ids, wts): top-k of the fp32 softmax of logits (T, nE) fp32, the lower
+// index first on equal values, wts renormalised to sum 1.
+std::tuple<Tensor, Tensor> moe_route(Tensor logits, int64_t top_k) {
+  const char* op = "moe_route";
+  TORCH_CHECK(logits.scalar_type() == torch::kFloat32 &&
+                  logits.is_contiguous() && logits.dim() == 2 &&
+                  logits.is_cuda(),
+              op, ": logits must be contiguous fp32 (T, nE) on a GPU");
+  const int64_t T = logits.size(0), nE = logits.size(1);
+  check_moe_topk(op, top_k, nE);
+  TORCH_CHECK(T * top_k < (1LL << 31), op, ": too many tokens");
+  auto ids = torch::empty({T, top_k}, logits.options().dtype(torch::kInt32));
+  auto wts = torch::empty({T, top_k}, logits.options());
+  if (T == 0) return {ids, wts};
+  launch_moe_route(logits.data_ptr<float>(), ids.data_ptr<int>(),
+                   wts.data_ptr<float>(), T, (int)nE, (int)top_k,
+                   cur_stream());
+  return {ids, wts};
+}
+
+// (row_pair, tile_expert): the (token, slot) pairs of ids (T, k) int32 in
+// expert order, stable, every expert's segment at a multiple of BM.
+// row_pair (tiles * BM) holds the pair t*k + j or -1, tile_expert (tiles)
+// the tile's expert or -1, tiles = moe_plan_tiles(T*k, BM, nE).
+std::tuple<Tensor, Tensor> moe_sort(Tensor ids, int64_t nE, int64_t BM) {
+  const char* op = "moe_sort";
+  check_moe_bm(op, BM);
+  TORCH_CHECK(ids.scalar_type() == torch::kInt32 && ids.is_contiguous() &&
+                  ids.dim() == 2 && ids.is_cuda(),
+              op, ": ids must be contiguous int32 (T, k) on a GPU");
+  check_moe_topk(op, ids.size(1), nE);
+  const int64_t npairs = ids.numel();
+  const int64_t ntiles = moe_plan_tiles(npairs, BM, nE);
+  TORCH_CHECK(npairs < (1LL << 31) && ntiles * BM < (1LL << 31), op,
+              ": too many tokens");
+  if (npairs == 0)
+    return {torch::full({ntiles * BM}, -1, ids.options()),
+            torch::full({ntiles}, -1, ids.options())};
+  auto row_pair = torch::empty({ntiles * BM}, ids.options());
+  auto tile_expert = torch::empty({ntiles}, ids.options());
+  auto hist =
+      torch::empty({(npairs + 255) / 256, MOE_MAX_EXPERTS}, ids.options());
+  launch_moe_sort(ids.data_ptr<int>(), hist.data_ptr<int>(),
+                  row_pair.data_ptr<int>(), tile_expert.data_ptr<int>(),
+                  npairs, (int)nE, (int)BM, (int)ntiles, cur_stream());
+  return {row_pair, tile_expert};
+}
+
+// h (tiles * BM, H) bf16 in sorted row order: silu(x[t] wg[e]^T) *
+// (x[t] wu[e]^T) with wg1[e] = [wg; wu] (2H, emb). Padding rows are not
+// written.
+Tensor moe_gate_up(Tensor x, Tensor row_pair, Tensor tile_expert,
+                   std::vector<Tensor> wg1, int64_t top_k, int64_t BM) {
+  const char* op = "moe_gate_up";
+  check_moe_bm(op, BM);
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.is_contiguous() &&
+                  x.dim() == 2 && x.is_cuda() && aligned16(x),
+              op, ": x must be contiguous bf16 (T, emb), 16-byte aligned, on "
+                  "a GPU");
+  const int64_t T = x.size(0), emb = x.size(1);
+  const int64_t nE = wg1.size();
+  const void* ptrs[MOE_MAX_EXPERTS] = {};
+  const int64_t H2 = check_moe_experts(op, "wg1", wg1, 0, emb, x, ptrs);
+  TORCH_CHECK(H2 % 2 == 0, op, ": wg1 must have 2H rows");
+  const int64_t H = H2 / 2;
+  check_moe_topk(op, top_k, nE);
+  const int64_t ntiles =
+      check_moe_sorted(op, row_pair, tile_expert, BM, T * top_k, nE, x);
+  check_moe_dims(op, emb, H, T * top_k, ntiles, BM);
+  auto h = torch::empty({ntiles * BM, H}, x.options());
+  if (T == 0) return h;
+  launch_moe_gate_up(ptrs, x.data_ptr(), row_pair.data_ptr<int>(),
+                     tile_expert.data_ptr<int>(), h.data_ptr(), (int)emb,
+                     (int)H, (int)(T * top_k), (int)top_k, (int)nE, (int)BM,
+                     (int)ntiles, cur_stream());
+  return h;
+}
+
+// ys (T*k, emb) fp32: row pair = wts[pair] * (h[p] w2[e]^T) for every real
+// sorted row p; every row is written exactly once.
+Tensor moe_down(Tensor h, Tensor row_pair, Tensor tile_expert, Tensor wts,
+                std::vector<Tensor> w2, int64_t T, int64_t BM) {
+  const char* op = "moe_down";
+  check_moe_bm(op, BM);
+  TORCH_CHECK(h.scalar_type() == torch::kBFloat16 && h.is_contiguous() &&
+                  h.dim() == 2 && h.is_cuda() && aligned16(h),
+              op, ": h must be contiguous bf16 (rows, H), 16-byte aligned, "
+                  "on a GPU");
+  const int64_t H = h.size(1);
+  const int64_t nE = w2.size();
+  const void* ptrs[MOE_MAX_EXPERTS] = {};
+  const int64_t emb = check_moe_experts(op, "w2", w2, 0, H, h, ptrs);
+  TORCH_CHECK(wts.scalar_type() == torch::kFloat32 && wts.is_contiguous() &&
+                  wts.dim() == 2 && wts.size(0) == T && wts.is_cuda() &&
+                  wts.device() == h.device(),
+              op, ": wts must be contiguous fp32 (T, k) on the GPU of h");
+  const int64_t top_k = wts.size(1);
+  check_moe_topk(op, top_k, nE);
+  const int64_t ntiles =
+      check_moe_sorted(op, row_pair, tile_expert, BM, T * top_k, nE, h);
+  TORCH_CHECK(h.size(0) == ntiles * BM, op, ": h must have ", ntiles * BM,
+              " rows");
+  check_moe_dims(op, emb, H, T * top_k, ntiles, BM);
+  auto ys = torch::empty({T * top_k, emb},
+                         h.options().dtype(torch::kFloat32));
+  if (T == 0) return ys;
+  launch_moe_down(ptrs, h.data_ptr(), row_pair.data_ptr<int>(),
+                  tile_expert.data_ptr<int>(), wts.data_ptr<float>(),
+                  ys.data_ptr<float>(), (int)emb, (int)H, (int)(T * top_k),
+                  (int)nE, (int)BM, (int)ntiles, cur_stream());
+  return ys;
+}
+
+// out (T, emb) bf16: the top_k slot rows of a token summed in slot order.
+Tensor moe_combine(Tensor ys, int64_t top_k) {
+  const char* op = "moe_combine";
+  TORCH_CHECK(ys.scalar_type() == torch::kFloat32 && ys.is_contiguous() &&
+                  ys.dim() == 2 && ys.is_cuda() && aligned16(ys),
+              op, ": ys must be contiguous fp32 (T*k, emb) on a GPU");
+  TORCH_CHECK(top_k >= 1 && top_k <= MOE_MAX_TOPK && ys.size(0) % top_k == 0,
+              op, ": ys must hold top_k rows per token");
+  const int64_t T = ys.size(0) / top_k, emb = ys.size(1);
+  TORCH_CHECK(emb % 8 == 0, op, ": emb must be a multiple of 8");
+  auto out = torch::empty({T, emb}, ys.options().dtype(torch::kBFloat16));
+  if (T == 0 || emb == 0) return out;
+  launch_moe_combine(ys.data_ptr<float>(), out.data_ptr(), T, (int)emb,
+                     (int)top_k, cur_stream());
+  return out;
+}
+
+// The whole chain with the plan's row tile: x (T, emb) bf16, logits (T, nE)
+// fp32, wg1[e] (2H, emb), w2[e] (emb, H). Every argument is checked before
+// the first launch.
+Tensor moe_mlp(Tensor x, Tensor logits, std::vector<Tensor> wg1,
+               std::vector<Tensor> w2, int64_t top_k) {
+  const char* op = "moe_mlp";
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.is_contiguous() &&
+                  x.dim() == 2 && x.is_cuda() && aligned16(x),
+              op, ": x must be contiguous bf16 (T, emb), 16-byte aligned, on "
+                  "a GPU");
+  const int64_t T = x.size(0), emb = x.size(1);
+  const int64_t nE = wg1.size();
+  TORCH_CHECK(w2.size() == wg1.size(), op,
+              ": wg1 and w2 must hold the same number of experts");
+  TORCH_CHECK(logits.scalar_type() == torch::kFloat32 &&
+                  logits.is_contiguous() && logits.dim() == 2 &&
+                  logits.size(0) == T && logits.size(1) == nE &&
+                  logits.device() == x.device(),
+              op, ": logits must be contiguous fp32 (T, nE) on the GPU of x");
+  const void* ptrs[MOE_MAX_EXPERTS] = {};
+  const int64_t H2 = check_moe_experts(op, "wg1", wg1, 0, emb, x, ptrs);
+  TORCH_CHECK(H2 % 2 == 0, op, ": wg1 must have 2H rows");
+  check_moe_experts(op, "w2", w2, emb, H2 / 2, x, ptrs);
+  check_moe_topk(op, top_k, nE);
+  const int64_t BM = moe_plan_bm(T, top_k, nE);
+  check_moe_dims(op, emb, H2 / 2, T * top_k,
+                 moe_plan_tiles(T * top_k, BM, nE), BM);
+  if (T == 0) return torch::empty_like(x);
+  auto [ids, wts] = moe_route(logits, top_k);
+  auto [row_pair, tile_expert] = moe_sort(ids, nE, BM);
+  auto h = moe_gate_up(x, row_pair, tile_expert, wg1, top_k, BM);
+  auto ys = moe_down(h, row_pair, tile_expert, wts, w2, T, BM);
+  ++moe_count;
+  return moe_combine(ys, top_k);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("moe_route", &moe_route, py::arg("logits"), py::arg("top_k"));
+  mod.def("moe_sort", &moe_sort, py::arg("ids"), py::arg("nE"),
+          py::arg("BM"));
+  mod.def("moe_gate_up", &moe_gate_up, py::arg("x"), py::arg("row_pair"),
+          py::arg("tile_expert"), py::arg("wg1"), py::arg("top_k"),
+          py::arg("BM"));
+  mod.def("moe_down", &moe_down, py::arg("h"), py::arg("row_pair"),
+          py::arg("tile_expert"), py::arg("wts"), py::arg("w2"), py::arg("T"),
+          py::arg("BM"));
+  mod.def("moe_combine", &moe_combine, py::arg("ys"), py::arg("top_k"));
+  mod.def("moe_mlp", &moe_mlp, py::arg("x"), py::arg("logits"),
+          py::arg("wg1"), py::arg("w2"), py::arg("top_k"));
+  mod.def("moe_plan_bm", &moe_plan_bm, py::arg("T"), py::arg("top_k"),
+          py::arg("nE"));
+  mod.def("moe_calls", &moe_calls);
   mod.def("ssd_chunk_state", &ssd_chunk_state, py::arg("B"), py::arg("xdtd"),
           py::arg("H"), py::arg("G"), py::arg("P"), py::arg("N"), py::arg("Q"),
           py::arg("out") = py::none());

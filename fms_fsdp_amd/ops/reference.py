@@ -103,6 +103,21 @@ def swiglu(gu):
     return (F.silu(g) * u).to(gu.dtype)
 
 
+def moe_mlp(x, ids, wts, wg1_list, w2_list):
+    """Routed SwiGLU MoE for given routing: x (T, emb), ids / wts (T, k),
+    wg1_list[e] (2H, emb) = [gate; up], w2_list[e] (emb, H) ->
+    out[t] = sum_j wts[t, j] * (silu(g) * u) w2[e]^T with e = ids[t, j],
+    (T, emb), computed in x's dtype."""
+    out = torch.zeros_like(x)
+    for j in range(ids.shape[1]):
+        for e in range(len(wg1_list)):
+            tok = (ids[:, j] == e).nonzero().flatten()
+            g, u = (x[tok] @ wg1_list[e].to(x.dtype).T).chunk(2, dim=-1)
+            y = (F.silu(g) * u) @ w2_list[e].to(x.dtype).T
+            out[tok] += wts[tok, j, None].to(x.dtype) * y
+    return out
+
+
 def linear_cross_entropy(x, weight, labels, ignore_index=-100):
     """x (b,s,e), weight (V,e), labels (b,s) -> mean CE over non-ignored."""
     logits = F.linear(x.float(), weight.float())

@@ -23,7 +23,7 @@ HIP_SOURCES = ["rmsnorm.hip", "rope.hip", "swiglu.hip", "cross_entropy.hip",
                "adamw.hip", "attention.hip", "causal_conv1d.hip", "ssd.hip",
                "gemm_nt.hip", "transpose.hip", "attn_decode.hip",
                "ssd_step.hip", "ssd_diag.hip", "ssd_diag_bwd.hip",
-               "ssd_state.hip", "ssd_state_bwd.hip", "ssd_yoff.hip"]
+               "ssd_state.hip", "ssd_state_bwd.hip", "ssd_yoff.hip", "moe.hip"]
 # extra hipcc flags per source: the ssd_diag kernels are built without the
 # packed fp32 VALU forms
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
@@ -31,7 +31,8 @@ HIP_EXTRA_FLAGS = {"ssd_diag.hip": NO_PACKED_FP32,
                    "ssd_diag_bwd.hip": NO_PACKED_FP32}
 # headers the .hip sources include: a newer header rebuilds every object
 HIP_HEADERS = ["common.h", "attn_sched.h", "attn_ws.h", "attn_frag.h",
-               "attn_decode_plan.h", "ssd_diag_frag.h", "transpose_tile.h"]
+               "attn_decode_plan.h", "ssd_diag_frag.h", "transpose_tile.h",
+               "moe_plan.h"]
 
 
 def compile_hip_objects():
