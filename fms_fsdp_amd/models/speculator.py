@@ -14,6 +14,8 @@ import math
 import torch
 import torch.nn as nn
 
+from fms_fsdp_amd import ops
+
 
 class LayerNormParameterized(nn.Module):
     def __init__(self, dim, elementwise_scale=True, elementwise_shift=True,
@@ -92,14 +94,31 @@ class MLPSpeculator(nn.Module):
         position t predicts inds[t + i + 1].
         Returns logits (n_predict, b, s, vocab)."""
         b, s, _ = state.shape
+        # ops.speculator_mode() "fused": each norm below is one kernel of
+        # ops/hip/layernorm.hip where ops.layernorm_act has one
+        fused = ops.speculator_mode() == "fused"
         if self.ln_input is not None:
-            state = self.ln_input(state) / math.sqrt(2)
+            ln = self.ln_input
+            if fused and ops.layernorm_act_has_kernel(state, ln.weight,
+                                                      ln.bias):
+                state = ops.layernorm_act(state, ln.weight, ln.bias, ln.eps,
+                                          out_scale=1 / math.sqrt(2))
+            else:
+                state = ln(state) / math.sqrt(2)
         out = []
         for i in range(self.n_predict):
-            z = self._pick(self.emb, i)(inds[:, i:i + s])
-            state = self._proj_for(i)(state) * self.state_weight \
-                + z * self.emb_weight
-            state = self.activation(self._pick(self.ln, i)(state))
+            emb, ln = self._pick(self.emb, i), self._pick(self.ln, i)
+            tok = inds[:, i:i + s]
+            state = self._proj_for(i)(state)
+            if fused and ops.layernorm_act_has_kernel(
+                    state, ln.weight, ln.bias, emb.weight, tok):
+                state = ops.layernorm_act(
+                    state, ln.weight, ln.bias, ln.eps, emb=emb.weight,
+                    tok=tok, sx=self.state_weight, se=self.emb_weight,
+                    gelu=True)
+            else:
+                state = state * self.state_weight + emb(tok) * self.emb_weight
+                state = self.activation(ln(state))
             out.append(self._pick(self.head, i)(state))
         return torch.stack(out, dim=0)
 

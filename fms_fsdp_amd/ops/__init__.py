@@ -238,6 +238,102 @@ def add_rmsnorm(x, res, weight, eps=1e-6):
 
 
 # --------------------------------------------------------------------------
+# LayerNorm + scaled embedding add + GELU (the MLPSpeculator's head step)
+# --------------------------------------------------------------------------
+_SPECULATOR_MODES = ("torch", "fused")
+_speculator_mode = None
+
+
+def speculator_mode(mode=None):
+    """Get/set the process-wide route of MLPSpeculator.forward: "torch"
+    (default) is its chain of eager elementwise ops, "fused" runs the
+    kernels of ops/hip/layernorm.hip where layernorm_act has one. None =
+    query. Returns the previous mode; until it is set, FMS_AMD_SPECULATOR
+    gives the mode."""
+    global _speculator_mode
+    prev = _speculator_mode
+    if prev is None:
+        prev = os.environ.get("FMS_AMD_SPECULATOR") or "torch"
+        if prev not in _SPECULATOR_MODES:
+            raise ValueError(f"FMS_AMD_SPECULATOR must be one of "
+                             f"{_SPECULATOR_MODES}, got {prev!r}")
+    if mode is not None:
+        if mode not in _SPECULATOR_MODES:
+            raise ValueError(f"speculator_mode: mode must be one of "
+                             f"{_SPECULATOR_MODES}, got {mode!r}")
+        _speculator_mode = mode
+    return prev
+
+
+class _LayerNormActFn(torch.autograd.Function):
+    """ln_act_fwd_kernel / ln_act_bwd_kernel over x2d (T, H) and tok (T).
+    Saves x, tok, mean and rstd; the backward recomputes the rest. The
+    embedding grad is aten's scatter of dz."""
+
+    @staticmethod
+    def forward(ctx, x2d, w, b, emb, tok, eps, sx, se, gelu, out_scale):
+        ext = _require_ext("layernorm_act")
+        y, mean, rstd = ext.ln_act_fwd(x2d, emb, tok, w, b, sx, se, eps, gelu,
+                                       out_scale)
+        ctx.save_for_backward(x2d, w, b, emb, tok, mean, rstd)
+        ctx.consts = (sx, se, gelu, out_scale)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2d, w, b, emb, tok, mean, rstd = ctx.saved_tensors
+        dx, dz, dw, db = _C.ln_act_bwd(dy.contiguous(), x2d, emb, tok, w, b,
+                                       mean, rstd, *ctx.consts)
+        demb = None
+        if emb is not None and ctx.needs_input_grad[3]:
+            demb = torch.ops.aten.embedding_dense_backward(
+                dz, tok, emb.shape[0], -1, False)
+        return (dx, dw.to(w.dtype), db.to(b.dtype), demb) + (None,) * 6
+
+
+def layernorm_act_has_kernel(x, w, b, emb=None, tok=None):
+    """True where layernorm_act runs layernorm.hip: bf16 x (..., H), w, b
+    and emb (V, H) contiguous and 16-byte aligned on one GPU, H a multiple
+    of 8 up to 8192, integer tok of x's leading shape on that GPU."""
+    if w is None or b is None or (emb is None) != (tok is None):
+        return False
+    ts = [x, w, b] if emb is None else [x, w, b, emb]
+    if not x.is_cuda or x.dim() < 1 or any(
+            t.dtype != torch.bfloat16 or t.device != x.device
+            or not t.is_contiguous() or t.data_ptr() % 16 for t in ts):
+        return False
+    H = x.shape[-1]
+    if H % 8 or not 8 <= H <= 8192 or x.numel() // H >= 2 ** 31 \
+            or w.numel() != H or b.numel() != H:
+        return False
+    if emb is not None and (
+            emb.dim() != 2 or emb.shape[1] != H
+            or not 1 <= emb.shape[0] < 2 ** 31
+            or tok.dtype not in (torch.int32, torch.int64)
+            or tok.device != x.device or tok.shape != x.shape[:-1]):
+        return False
+    return True
+
+
+def layernorm_act(x, w, b, eps, emb=None, tok=None, sx=1.0, se=0.0,
+                  gelu=False, out_scale=1.0):
+    """act(LN(x * sx + emb[tok] * se) * w + b) * out_scale over the last dim
+    in x's dtype (reference.layernorm_act has the definition). One kernel
+    forward and one backward where layernorm_act_has_kernel; CPU, fp32,
+    fp16 and the other shapes run the torch expression in fp32."""
+    if layernorm_act_has_kernel(x, w, b, emb, tok):
+        H = x.shape[-1]
+        tok1d = None if tok is None else tok.reshape(-1).contiguous()
+        y = _LayerNormActFn.apply(x.view(-1, H), w, b, emb, tok1d, eps, sx,
+                                  se, gelu, out_scale)
+        return y.view(x.shape)
+    return reference.layernorm_act(
+        x.float(), w.float(), b.float(), eps,
+        None if emb is None else emb.float(), tok, sx, se, gelu,
+        out_scale).to(x.dtype)
+
+
+# --------------------------------------------------------------------------
 # RoPE (half-rotation convention; cos/sin tables (s, d/2) fp32)
 # --------------------------------------------------------------------------
 def _row_view_ok(t):

@@ -156,6 +156,15 @@ void launch_moe_down(const void* const*, const void*, const int*, const int*,
                      hipStream_t);
 void launch_moe_combine(const float*, void*, long long, int, int,
                         hipStream_t);
+int ln_act_bwd_nparts(int);
+void launch_ln_act_fwd(const void*, const void*, const void*, int,
+                       const void*, const void*, void*, float*, float*, int,
+                       int, int, float, float, float, int, float,
+                       hipStream_t);
+void launch_ln_act_bwd(const void*, const void*, const void*, const void*,
+                       int, const void*, const void*, const float*,
+                       const float*, void*, void*, float*, int, float*, int,
+                       int, int, float, float, int, float, hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -2052,6 +2061,125 @@ std::vector<Tensor> ssd_state_pass_bwd_doc(
                                  want_dinitial, doc_start, l);
 }
 
+// ---- LayerNorm + embedding add + GELU (layernorm.hip) -----------------------
+static int64_t ln_act_count = 0;
+
+// Forward launches of ln_act_fwd so far.
+int64_t ln_act_calls() { return ln_act_count; }
+
+struct LnActArgs {
+  int rows, H, V;
+  const void* emb;
+  const void* tok;
+  int tok64;
+};
+
+// Everything the kernels assume, checked before any launch. Token ids are
+// clamped in the kernels, so no tensor contents can move an address.
+static LnActArgs check_ln_act(const char* op, const Tensor& x,
+                              const c10::optional<Tensor>& emb,
+                              const c10::optional<Tensor>& tok,
+                              const Tensor& w, const Tensor& b) {
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.is_contiguous() &&
+                  x.dim() == 2 && x.is_cuda() && aligned16(x),
+              op, ": x must be contiguous bf16 (T, H), 16-byte aligned, on a "
+                  "GPU");
+  const int64_t T = x.size(0), H = x.size(1);
+  TORCH_CHECK(H % 8 == 0 && H >= 8 && H <= 8192, op,
+              ": H must be a multiple of 8 in [8, 8192], got ", H);
+  TORCH_CHECK(T < (1LL << 31), op, ": too many rows");
+  for (const Tensor* p : {&w, &b})
+    TORCH_CHECK(p->scalar_type() == torch::kBFloat16 && p->is_contiguous() &&
+                    p->numel() == H && p->device() == x.device() &&
+                    aligned16(*p),
+                op, ": w and b must be contiguous bf16 with H elements, "
+                    "16-byte aligned, on the GPU of x");
+  TORCH_CHECK(emb.has_value() == tok.has_value(), op,
+              ": emb and tok are given together or not at all");
+  LnActArgs a{(int)T, (int)H, 0, nullptr, nullptr, 0};
+  if (emb.has_value()) {
+    TORCH_CHECK(emb->scalar_type() == torch::kBFloat16 &&
+                    emb->is_contiguous() && emb->dim() == 2 &&
+                    emb->device() == x.device() && aligned16(*emb),
+                op, ": emb must be contiguous bf16 (V, H), 16-byte aligned, "
+                    "on the GPU of x");
+    TORCH_CHECK(emb->size(1) == H && emb->size(0) >= 1 &&
+                    emb->size(0) < (1LL << 31),
+                op, ": emb must have H = ", H, " columns and 1 to 2^31-1 rows");
+    TORCH_CHECK((tok->scalar_type() == torch::kInt32 ||
+                 tok->scalar_type() == torch::kInt64) &&
+                    tok->is_contiguous() && tok->numel() == T &&
+                    tok->device() == x.device(),
+                op, ": tok must be contiguous int32 or int64 with one id per "
+                    "row on the GPU of x");
+    a.V = (int)emb->size(0);
+    a.emb = emb->data_ptr();
+    a.tok = tok->data_ptr();
+    a.tok64 = tok->scalar_type() == torch::kInt64;
+  }
+  return a;
+}
+
+// (y, mean, rstd) of y = act(LN(x * sx + emb[tok] * se) * w + b) * out_scale
+// per row of x (T, H) bf16; act is the exact GELU or the identity.
+std::tuple<Tensor, Tensor, Tensor> ln_act_fwd(
+    Tensor x, c10::optional<Tensor> emb, c10::optional<Tensor> tok, Tensor w,
+    Tensor b, double sx, double se, double eps, bool gelu, double out_scale) {
+  const LnActArgs a = check_ln_act("ln_act_fwd", x, emb, tok, w, b);
+  auto f32 = x.options().dtype(torch::kFloat32);
+  auto y = torch::empty_like(x);
+  auto mean = torch::empty({a.rows}, f32);
+  auto rstd = torch::empty({a.rows}, f32);
+  if (a.rows == 0) return {y, mean, rstd};
+  launch_ln_act_fwd(x.data_ptr(), a.emb, a.tok, a.tok64, w.data_ptr(),
+                    b.data_ptr(), y.data_ptr(), mean.data_ptr<float>(),
+                    rstd.data_ptr<float>(), a.rows, a.H, a.V, (float)sx,
+                    (float)se, (float)eps, gelu ? 1 : 0, (float)out_scale,
+                    cur_stream());
+  ++ln_act_count;
+  return {y, mean, rstd};
+}
+
+// (dx, dz or None, dw, db): dx and dz (T, H) bf16 are the grads of x and of
+// the gathered embedding rows, dw and db (H) fp32. Deterministic: per-block
+// fp32 partials summed in a fixed order.
+std::tuple<Tensor, c10::optional<Tensor>, Tensor, Tensor> ln_act_bwd(
+    Tensor dy, Tensor x, c10::optional<Tensor> emb, c10::optional<Tensor> tok,
+    Tensor w, Tensor b, Tensor mean, Tensor rstd, double sx, double se,
+    bool gelu, double out_scale) {
+  const char* op = "ln_act_bwd";
+  const LnActArgs a = check_ln_act(op, x, emb, tok, w, b);
+  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 && dy.is_contiguous() &&
+                  dy.sizes() == x.sizes() && dy.device() == x.device() &&
+                  aligned16(dy),
+              op, ": dy must be contiguous bf16 of x's shape, 16-byte "
+                  "aligned, on the GPU of x");
+  for (const Tensor* s : {&mean, &rstd})
+    TORCH_CHECK(s->scalar_type() == torch::kFloat32 && s->is_contiguous() &&
+                    s->numel() == a.rows && s->device() == x.device(),
+                op, ": mean and rstd must be contiguous fp32 with one element "
+                    "per row on the GPU of x");
+  auto f32 = x.options().dtype(torch::kFloat32);
+  auto dx = torch::empty_like(x);
+  c10::optional<Tensor> dz;
+  if (a.emb != nullptr) dz = torch::empty_like(x);
+  if (a.rows == 0) {
+    auto z = torch::zeros({2, a.H}, f32);
+    return {dx, dz, z[0], z[1]};
+  }
+  const int nparts = ln_act_bwd_nparts(a.rows);
+  auto part = torch::empty({nparts, 2, a.H}, f32);
+  auto dwdb = torch::empty({2, a.H}, f32);
+  launch_ln_act_bwd(dy.data_ptr(), x.data_ptr(), a.emb, a.tok, a.tok64,
+                    w.data_ptr(), b.data_ptr(), mean.data_ptr<float>(),
+                    rstd.data_ptr<float>(), dx.data_ptr(),
+                    dz.has_value() ? dz->data_ptr() : nullptr,
+                    part.data_ptr<float>(), nparts, dwdb.data_ptr<float>(),
+                    a.rows, a.H, a.V, (float)sx, (float)se, gelu ? 1 : 0,
+                    (float)out_scale, cur_stream());
+  return {dx, dz, dwdb[0], dwdb[1]};
+}
+
 // ---- routed MoE MLP, inference forward (moe.hip) ---------------------------
 static int64_t moe_count = 0;
 
@@ -2291,6 +2419,15 @@ Tensor moe_mlp(Tensor x, Tensor logits, std::vector<Tensor> wg1,
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("ln_act_fwd", &ln_act_fwd, py::arg("x"), py::arg("emb"),
+          py::arg("tok"), py::arg("w"), py::arg("b"), py::arg("sx"),
+          py::arg("se"), py::arg("eps"), py::arg("gelu"),
+          py::arg("out_scale"));
+  mod.def("ln_act_bwd", &ln_act_bwd, py::arg("dy"), py::arg("x"),
+          py::arg("emb"), py::arg("tok"), py::arg("w"), py::arg("b"),
+          py::arg("mean"), py::arg("rstd"), py::arg("sx"), py::arg("se"),
+          py::arg("gelu"), py::arg("out_scale"));
+  mod.def("ln_act_calls", &ln_act_calls);
   mod.def("moe_route", &moe_route, py::arg("logits"), py::arg("top_k"));
   mod.def("moe_sort", &moe_sort, py::arg("ids"), py::arg("nE"),
           py::arg("BM"));

@@ -16,6 +16,22 @@ def rmsnorm(x, weight, eps):
     return (y * weight.float()).to(x.dtype)
 
 
+def layernorm_act(x, w, b, eps, emb=None, tok=None, sx=1.0, se=0.0,
+                  gelu=False, out_scale=1.0):
+    """act(LN(x * sx + emb[tok] * se) * w + b) * out_scale over the last
+    dim, act the exact (erf) GELU or the identity; token ids are clamped to
+    emb's rows. Computed in the dtype of the inputs and not rounded: run on
+    float64 copies it is the oracle of the layernorm.hip kernels."""
+    v = x * sx
+    if emb is not None:
+        v = v + emb[tok.clamp(0, emb.shape[0] - 1)] * se
+    c = v - v.mean(-1, keepdim=True)
+    n = c * torch.rsqrt(c.square().mean(-1, keepdim=True) + eps) * w + b
+    if gelu:
+        n = n * 0.5 * (1.0 + torch.erf(n * 0.5 ** 0.5))
+    return n * out_scale
+
+
 def rope_apply(q, k, cos, sin):
     """q (b,s,h,d), k (b,s,kvh,d); cos/sin (s, d/2) fp32. Half-rotation
     (HF) convention: (x1, x2) -> (x1*cos - x2*sin, x2*cos + x1*sin) with

@@ -23,7 +23,8 @@ HIP_SOURCES = ["rmsnorm.hip", "rope.hip", "swiglu.hip", "cross_entropy.hip",
                "adamw.hip", "attention.hip", "causal_conv1d.hip", "ssd.hip",
                "gemm_nt.hip", "transpose.hip", "attn_decode.hip",
                "ssd_step.hip", "ssd_diag.hip", "ssd_diag_bwd.hip",
-               "ssd_state.hip", "ssd_state_bwd.hip", "ssd_yoff.hip", "moe.hip"]
+               "ssd_state.hip", "ssd_state_bwd.hip", "ssd_yoff.hip", "moe.hip",
+               "layernorm.hip"]
 # extra hipcc flags per source: the ssd_diag kernels are built without the
 # packed fp32 VALU forms
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
