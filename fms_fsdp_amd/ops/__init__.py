@@ -882,9 +882,12 @@ def attention_cached(q, k, v, cache, cos=None, sin=None):
       - prefill (the cache was empty): attention_causal on views of the
         cache rows just written;
       - s == 1: attention_decode;
-      - s > 1 on a non-empty cache (chunked prefill): the fp32 reference
-        with the causal mask aligned bottom right. Rare; correct, not
-        fast.
+      - s > 1 on a non-empty cache (verifying a speculator's n_predict
+        proposals in one step, chunked prefill): the causal mask aligned
+        bottom right. bf16/fp16 on a GPU with head_dim 64 or 128 and at
+        most 64 heads per kv head run attn_decode_mq_kernel, one sweep of
+        the cache for all s positions of a kv head; everything else the
+        fp32 reference.
     No backward (inference only)."""
     _decode_no_grad(q, k, v)
     if os.environ.get("FMS_AMD_DECODE") == "sdpa":
@@ -907,6 +910,12 @@ def attention_cached(q, k, v, cache, cos=None, sin=None):
             # batch dim with the stride of n rows
             kc, vc = kc[0].unsqueeze(0), vc[0].unsqueeze(0)
         return attention_causal(qr, kc, vc)
+    if (qr.is_cuda and qr.dtype == torch.bfloat16
+            and qr.shape[3] in (64, 128)
+            and qr.shape[2] <= 64 * cache.k.shape[2]):
+        ext = _require_ext("attention_cached")
+        o, _ = ext.attn_decode_mq(qr.contiguous(), cache.k, cache.v, n, 0)
+        return o
     return reference.attention_cached(qr, cache.k[:, :n], cache.v[:, :n])
 
 

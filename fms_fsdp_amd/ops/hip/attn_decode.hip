@@ -10,6 +10,9 @@
 //  attn_decode_kernel<D>        q (b, 1, h, d) against cache rows
 //      [0, kv_len), one workgroup per (batch row, kv head, 32-head column
 //      block, split).
+//  attn_decode_mq_kernel<D>     q (b, s, h, d), the last s cache rows, with
+//      the causal mask aligned bottom right: (query, head) pairs packed
+//      into the 32 columns, one sweep of K/V per column block.
 //  attn_decode_combine_kernel   merges the splits' fp32 partials in split
 //      order and rounds to bf16 once.
 #include "common.h"
@@ -366,6 +369,308 @@ __global__ __launch_bounds__(256, 2) void attn_decode_kernel(
 }
 
 // ---------------------------------------------------------------------
+// Multi-query decode attention (speculator verify, chunked prefill):
+// q (b, s, h, d) holds the LAST s of the kv_len cache rows, already
+// appended; query qi sees keys j <= lim(qi) = kv_len - s + qi (causal,
+// aligned bottom right). A sibling of attn_decode_kernel with the same
+// tile loop, V image, wave merge and split workspace; what differs:
+//
+// Columns. The 32 MFMA columns hold (query position, head) pairs of one
+// kv head in query-major order, c = qi*G + g over s*G columns, zero Q
+// beyond; column block cb takes columns [32cb, 32cb + 32). One sweep of
+// K/V serves every pair of the block. Every lane owns one pair and keeps
+// its lim in one register. q, o and lse are addressed by the row
+// (b*s + qi)*h + kvh*G + g.
+//
+// Bounds. A block's queries are consecutive, qi_min..qi_max, so it sweeps
+// the tiles [0, lim(qi_max)/32 + 1) only; splits divide that range. The
+// binding clamps splits to the tile count of kv_len - s + 1 keys (the keys
+// query 0 sees), which is at most every block's tile count.
+//
+// Mask. A tile whose last key is > lim(qi_min) (which covers every tile
+// reaching kv_len) is `partial`: scores of keys > lim are replaced by a
+// select before the max, their P by a select after the exponential. All
+// other tiles run the unmasked instruction stream. Row indices stay
+// clamped to kv_len - 1 as in attn_decode_kernel.
+//
+// P goes to the PV mfma as two bf16 terms, hi = bf16(P) and
+// lo = bf16(P - hi) (the difference is exact in fp32), so the numerator
+// carries 2^-16 per term where one rounding carries up to 2^-8 (half a
+// bf16 ulp at the bottom of a binade). A query that sees three keys with
+// V entries that cancel has nothing to average that rounding away; the
+// two extra mfmas per output tile hide behind the K/V loads.
+//
+// Softmax pitfall (attn_decode_kernel cannot hit it): a wave's first tile
+// can be wholly masked for some columns of its block and visible for
+// others (s 33, G 1, kv_len 64: wave 1's tile is keys 32..63, column
+// qi = 0 has lim 31). Such a column keeps m_run = -1e30, and
+// exp2(-1e30 - (-1e30)) = 1 for every masked key: the select after the
+// exponential keeps that 1 out of l and P, so the wave ends with l = 0,
+// O = 0 for the column and the merge gives it the weight
+// exp2(-1e30 - m_tot) = 0. Key 0 is visible to every query, so some wave
+// of split 0 holds a real maximum; a split whose column stayed at
+// (m = -1e30, l = 0) gets the weight 0 from the combine in the same way.
+// ---------------------------------------------------------------------
+template <int D>
+__global__ __launch_bounds__(256, 2) void attn_decode_mq_kernel(
+    const short* __restrict__ qg, const short* __restrict__ kcg,
+    const short* __restrict__ vcg, short* __restrict__ og,
+    float* __restrict__ lseg, float* __restrict__ ws_o,
+    float* __restrict__ ws_ml, int S, int H, int KVH, int kv_len,
+    long long capacity, int splits, int ncb, float scale) {
+  constexpr int NC = D / 16;    // QK^T k-chunks = 16-byte V loads per lane
+  constexpr int NT = D / 32;    // 32-wide output tiles
+  constexpr int KT = ATTN_DECODE_KEY_TILE;
+  constexpr int VIMG = KT * D * 2;          // bytes of one wave's V image
+  constexpr int CPR = D / 8;                // 16-byte chunks per V row
+  constexpr int RPI = 64 / CPR;             // V rows per load instruction
+  static_assert(KT == 32 && NC * RPI == KT, "tile shape");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col = lane & 31;
+  const int hb = lane >> 5;
+
+  int bid = blockIdx.x;
+  const int split = bid % splits;
+  bid /= splits;
+  const int cb = bid % ncb;
+  bid /= ncb;
+  const int kvh = bid % KVH;
+  const long long b = bid / KVH;
+
+  const int G = H / KVH;
+  const int c = cb * 32 + col;              // (query, head) pair of the lane
+  const bool valid = c < S * G;
+  const int qi = min(c / G, S - 1);         // zero-Q columns: any query
+  const int g = c - (c / G) * G;
+  const int lim = kv_len - S + qi;          // last key this lane's query sees
+  // the block's query range (wave-uniform)
+  const int qi_min = cb * 32 / G;
+  const int qi_max = min((cb * 32 + 31) / G, S - 1);
+  const int lim_min = kv_len - S + qi_min;
+  // output row of the pair
+  const long long row = (b * S + qi) * H + (long long)kvh * G + g;
+  const float scale2 = scale * 1.4426950408889634f;
+
+  // Q -> B-fragments: B[k = d][j = pair], k = hb*8 + e per 16-wide chunk
+  bf16x8v qb[NC];
+  {
+    const short* qp = qg + row * D + hb * 8;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      bf16x8v qv = (bf16x8v)((__bf16)0.f);
+      if (valid) qv = *(const bf16x8v*)(qp + i * 16);
+      qb[i] = qv;
+    }
+  }
+
+  // the block's tile range, this split's share of it (never empty:
+  // splits <= (kv_len - S)/32 + 1 <= ntile) and the wave's share of that
+  const int ntile = (kv_len - S + qi_max) / KT + 1;
+  const int t_lo = (int)((long long)split * ntile / splits);
+  const int t_hi = (int)((long long)(split + 1) * ntile / splits);
+
+  const long long rs = (long long)KVH * D;  // cache row stride
+  const long long cbase = (b * capacity * KVH + kvh) * D;
+  const short* kbase = kcg + cbase + hb * 8;
+  const int vrow0 = lane / CPR;
+  const int vcol = (lane % CPR) * 8;
+  const short* vbase = vcg + cbase + vcol;
+  char* vimg = smem + wid * VIMG;
+  int voff[NC];
+#pragma unroll
+  for (int i = 0; i < NC; ++i)
+    voff[i] = SUBT_OFF(i * RPI + vrow0, vcol, KT / 4);
+  // transpose-read base of the PV A-operand, as in attn_decode_kernel
+  const int pvswz = (((lane & 15) * 8) ^ (16 * hb)) + hb * 256 +
+                    (col >> 4) * (KT / 4) * 128;
+
+  bf16x8v kn[NC];
+  f32x4v vn[NC];
+  auto load_tile = [&](int t) {
+    const int last = kv_len - 1;
+    const long long krow = min(t * KT + col, last);
+    const short* kp = kbase + krow * rs;
+#pragma unroll
+    for (int i = 0; i < NC; ++i) kn[i] = *(const bf16x8v*)(kp + i * 16);
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      const long long vrow = min(t * KT + i * RPI + vrow0, last);
+      vn[i] = *(const f32x4v*)(vbase + vrow * rs);
+    }
+  };
+
+  f32x16 accO[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) accO[t] = (f32x16)(0.f);
+  float m_run = -1e30f, l_run = 0.f;
+
+  int tile = t_lo + wid;
+  if (tile < t_hi) load_tile(tile);
+  for (; tile < t_hi; tile += 4) {
+    f32x16 accS = (f32x16)(0.f);
+#pragma unroll
+    for (int i = 0; i < NC; ++i)
+      accS = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kn[i], qb[i], accS, 0,
+                                                     0, 0);
+    // DS ops of a wave complete in order (see attn_decode_kernel)
+#pragma unroll
+    for (int i = 0; i < NC; ++i) *(f32x4v*)(vimg + voff[i]) = vn[i];
+    if (tile + 4 < t_hi) load_tile(tile + 4);
+
+    const int key0 = tile * KT;
+    // wave-uniform; lim_min < kv_len, so this covers keys >= kv_len too
+    const bool partial = key0 + KT - 1 > lim_min;
+    float p[16];
+    float mt = -1e30f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float sv = accS[r] * scale2;
+      if (partial && key0 + DROW(r, hb) > lim) sv = -1e30f;
+      p[r] = sv;
+      mt = fmaxf(mt, sv);
+    }
+    mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+    const float m_new = fmaxf(m_run, mt);
+    const float alpha = exp2f(m_run - m_new);
+    m_run = m_new;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) accO[t][r] *= alpha;
+    float s_own = 0.f;
+    float plo[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float e = exp2f(p[r] - m_run);
+      // select, never multiply; also the pitfall's exp2(0) = 1
+      if (partial && key0 + DROW(r, hb) > lim) e = 0.f;
+      p[r] = e;
+      plo[r] = e - bf2f(f2bf(e));     // exact in fp32
+      s_own += e;
+    }
+    l_run = l_run * alpha + s_own + __shfl_xor(s_own, 32, 64);
+
+    const bf16x8v pb0 = pack_pT_chunk(p);
+    const bf16x8v pb1 = pack_pT_chunk(p + 8);
+    const bf16x8v pl0 = pack_pT_chunk(plo);
+    const bf16x8v pl1 = pack_pT_chunk(plo + 8);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      // column blocks 2t, 2t+1; keys 0..15 then 16..31; low parts first
+      const int o = pvswz + t * 2 * (KT / 4) * 128;
+      const TR4 fr = tr_read4(vimg, o, o + 128, o + 512, o + 640);
+      accO[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr.a, pl0, accO[t],
+                                                        0, 0, 0);
+      accO[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr.b, pl1, accO[t],
+                                                        0, 0, 0);
+      accO[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr.a, pb0, accO[t],
+                                                        0, 0, 0);
+      accO[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr.b, pb1, accO[t],
+                                                        0, 0, 0);
+    }
+  }
+
+  // ---- merge the four waves: a wave without tiles, or whose tiles were
+  // all masked for this column, has m = -1e30, l = 0, O = 0 ----
+  float* sm_m = (float*)(smem + 4 * VIMG);    // [4][32]
+  float* sm_l = sm_m + 128;                   // [4][32]
+  if (hb == 0) {
+    sm_m[wid * 32 + col] = m_run;
+    sm_l[wid * 32 + col] = l_run;
+  }
+  __syncthreads();      // also: every wave is done with its V image
+  float m_tot = -1e30f;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) m_tot = fmaxf(m_tot, sm_m[w * 32 + col]);
+  float l_tot = 0.f;
+#pragma unroll
+  for (int w = 0; w < 4; ++w)
+    l_tot += sm_l[w * 32 + col] * exp2f(sm_m[w * 32 + col] - m_tot);
+  const float f = exp2f(m_run - m_tot);
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accO[t][r] *= f;
+
+  // (w0 + w2) + (w1 + w3) in the LDS of the four V images
+  float* red = (float*)smem;
+  constexpr int RED = NT * 16 * 64;
+  if (wid >= 2) {
+    float* dst = red + (wid - 2) * RED + lane;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dst[(t * 16 + r) * 64] = accO[t][r];
+  }
+  __syncthreads();
+  if (wid < 2) {
+    const float* src = red + wid * RED + lane;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) accO[t][r] += src[(t * 16 + r) * 64];
+  }
+  __syncthreads();
+  if (wid == 1) {
+    float* dst = red + lane;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dst[(t * 16 + r) * 64] = accO[t][r];
+  }
+  __syncthreads();
+  if (wid != 0 || !valid) return;
+  {
+    const float* src = red + lane;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) accO[t][r] += src[(t * 16 + r) * 64];
+  }
+
+  // ---- epilogue: lane (col, hb), register r holds dv = 32t + DROW(r, hb)
+  if (splits == 1) {
+    const float inv_l = 1.f / l_tot;
+    short* op = og + row * D;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int j4 = 0; j4 < 4; ++j4) {
+        const int dv0 = t * 32 + 8 * j4 + 4 * hb;
+        bf16x4 w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          w.v[j] = f2bf(accO[t][j4 * 4 + j] * inv_l);
+        *(bf16x4*)(op + dv0) = w;
+      }
+    }
+    if (hb == 0)
+      lseg[row] = (m_tot + __log2f(l_tot)) * 0.6931471805599453f;
+  } else {
+    float* op = ws_o + (row * splits + split) * D;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int j4 = 0; j4 < 4; ++j4) {
+        const int dv0 = t * 32 + 8 * j4 + 4 * hb;
+        f32x4 w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w.v[j] = accO[t][j4 * 4 + j];
+        *(f32x4*)(op + dv0) = w;
+      }
+    }
+    if (hb == 0) {
+      float* ml = ws_ml + (row * splits + split) * 2;
+      ml[0] = m_tot;
+      ml[1] = l_tot;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------
 // Combine. One thread per (b, h) and 4 output columns: the splits'
 // maxima, then l and O accumulated in split order 0..splits-1, one bf16
 // rounding. No atomics: two calls give identical bits.
@@ -447,6 +752,36 @@ void launch_attn_decode(const void* q, const void* kcache, const void* vcache,
         scale);
   if (splits > 1) {
     const long long total4 = (long long)b * h * d / 4;
+    const int block = 256;
+    attn_decode_combine_kernel<<<(int)((total4 + block - 1) / block), block,
+                                 0, stream>>>(ws_o, ws_ml, (short*)o, lse,
+                                              splits, d, total4);
+  }
+}
+
+// s query positions per row; splits >= 1 and <= the tile count of
+// kv_len - s + 1 keys (the binding clamps); the workspaces hold
+// b*s*h*splits rows.
+void launch_attn_decode_mq(const void* q, const void* kcache,
+                           const void* vcache, void* o, float* lse,
+                           float* ws_o, float* ws_ml, int b, int s, int h,
+                           int kvh, int d, int kv_len, long long capacity,
+                           int splits, float scale, hipStream_t stream) {
+  const int ncb = (s * (h / kvh) + 31) / 32;
+  const int grid = b * kvh * ncb * splits;
+  const size_t lds = (size_t)4 * ATTN_DECODE_KEY_TILE * d * 2 + 1024;
+  if (d == 64)
+    attn_decode_mq_kernel<64><<<grid, 256, lds, stream>>>(
+        (const short*)q, (const short*)kcache, (const short*)vcache,
+        (short*)o, lse, ws_o, ws_ml, s, h, kvh, kv_len, capacity, splits,
+        ncb, scale);
+  else
+    attn_decode_mq_kernel<128><<<grid, 256, lds, stream>>>(
+        (const short*)q, (const short*)kcache, (const short*)vcache,
+        (short*)o, lse, ws_o, ws_ml, s, h, kvh, kv_len, capacity, splits,
+        ncb, scale);
+  if (splits > 1) {
+    const long long total4 = (long long)b * s * h * d / 4;
     const int block = 256;
     attn_decode_combine_kernel<<<(int)((total4 + block - 1) / block), block,
                                  0, stream>>>(ws_o, ws_ml, (short*)o, lse,

@@ -64,6 +64,9 @@ void launch_kv_append(const void*, const void*, const void*, void*, void*,
 void launch_attn_decode(const void*, const void*, const void*, void*, float*,
                         float*, float*, int, int, int, int, int, long long,
                         int, float, hipStream_t);
+void launch_attn_decode_mq(const void*, const void*, const void*, void*,
+                           float*, float*, float*, int, int, int, int, int,
+                           int, long long, int, float, hipStream_t);
 int attn_sched_mode(int);
 int attn_dkv_mode(int);
 long long attn_bwd_ws_limit(long long);
@@ -803,6 +806,68 @@ std::tuple<Tensor, Tensor> attn_decode(Tensor q, Tensor kcache, Tensor vcache,
                      splits > 1 ? ws_ml.data_ptr<float>() : nullptr, (int)b,
                      (int)h, (int)kvh, (int)d, (int)kv_len, cap, (int)splits,
                      1.f / sqrtf((float)d), cur_stream());
+  return {o, lse};
+}
+
+// q (b, s, h, d) = the LAST s of the kv_len cache rows (already appended):
+// query qi sees keys j <= kv_len - s + qi. Returns (o (b,s,h,d) bf16,
+// lse (b, s, h) fp32, natural log). splits as in attn_decode, planned over
+// the kvh * ceil(s*G/32) workgroups of a batch row and clamped to the key
+// tiles the first query sees, so that no split of any column block is empty.
+std::tuple<Tensor, Tensor> attn_decode_mq(Tensor q, Tensor kcache,
+                                          Tensor vcache, int64_t kv_len,
+                                          int64_t splits) {
+  TORCH_CHECK(q.is_cuda(), "attn_decode_mq: q must be on a GPU");
+  CHECK_BF16_CONTIG(q);
+  check_kv_cache(kcache, vcache, q.device());
+  TORCH_CHECK(q.dim() == 4, "attn_decode_mq: q must be (b, s, h, d)");
+  const int64_t b = q.size(0), s = q.size(1), h = q.size(2), d = q.size(3);
+  const int64_t cap = kcache.size(1), kvh = kcache.size(2);
+  TORCH_CHECK(kcache.size(0) == b && kcache.size(3) == d,
+              "attn_decode_mq: cache shape does not match q");
+  TORCH_CHECK(d == 64 || d == 128,
+              "attn_decode_mq: head_dim must be 64 or 128");
+  TORCH_CHECK(kv_len >= 1 && kv_len <= cap, "attn_decode_mq: kv_len ", kv_len,
+              " outside [1, capacity ", cap, "]");
+  TORCH_CHECK(s >= 1 && s <= kv_len, "attn_decode_mq: ", s,
+              " query positions outside [1, kv_len ", kv_len, "]");
+  TORCH_CHECK(kvh >= 1 && h % kvh == 0,
+              "attn_decode_mq: kvheads must divide nheads");
+  TORCH_CHECK(h / kvh <= 64,
+              "attn_decode_mq: at most 64 query heads per kv head");
+  TORCH_CHECK(aligned16(q), "attn_decode_mq: q must be 16-byte aligned");
+  TORCH_CHECK(splits >= 0, "attn_decode_mq: splits must be >= 0");
+  TORCH_CHECK(kv_len < (1LL << 31) - 64, "attn_decode_mq: kv_len too large");
+  auto o = torch::empty_like(q);
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto lse = torch::empty({b, s, h}, f32);
+  if (b == 0) return {o, lse};
+  const int64_t ncb = (s * (h / kvh) + 31) / 32;
+  if (splits == 0) {
+    int n_cu = 0;
+    TORCH_CHECK(hipDeviceGetAttribute(&n_cu,
+                                      hipDeviceAttributeMultiprocessorCount,
+                                      q.get_device()) == hipSuccess,
+                "attn_decode_mq: cannot query the compute unit count");
+    splits = attn_decode_plan(b, kvh * ncb, kv_len, n_cu);
+  }
+  splits = attn_decode_clamp_splits(splits, kv_len - s + 1);
+  TORCH_CHECK(b * kvh * ncb * splits < (1LL << 31) &&
+                  ncb * 32 < (1LL << 31) &&
+                  b * s * h * d / 4 < (1LL << 31) * 256,
+              "attn_decode_mq: too many workgroups for one grid");
+  Tensor ws_o, ws_ml;
+  if (splits > 1) {
+    ws_o = torch::empty({b, s, h, splits, d}, f32);
+    ws_ml = torch::empty({b, s, h, splits, 2}, f32);
+  }
+  launch_attn_decode_mq(q.data_ptr(), kcache.data_ptr(), vcache.data_ptr(),
+                        o.data_ptr(), lse.data_ptr<float>(),
+                        splits > 1 ? ws_o.data_ptr<float>() : nullptr,
+                        splits > 1 ? ws_ml.data_ptr<float>() : nullptr,
+                        (int)b, (int)s, (int)h, (int)kvh, (int)d, (int)kv_len,
+                        cap, (int)splits, 1.f / sqrtf((float)d),
+                        cur_stream());
   return {o, lse};
 }
 
@@ -2532,6 +2597,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("cos") = pybind11::none(),
           pybind11::arg("sin") = pybind11::none());
   mod.def("attn_decode", &attn_decode, pybind11::arg("q"),
+          pybind11::arg("kcache"), pybind11::arg("vcache"),
+          pybind11::arg("kv_len"), pybind11::arg("splits") = 0);
+  mod.def("attn_decode_mq", &attn_decode_mq, pybind11::arg("q"),
           pybind11::arg("kcache"), pybind11::arg("vcache"),
           pybind11::arg("kv_len"), pybind11::arg("splits") = 0);
   mod.def("attn_decode_plan", &attn_decode_plan_py);
